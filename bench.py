@@ -11,6 +11,7 @@ outputs resident in HBM (for N > 1 it includes the RCCL gather, pipelined in
 chunks behind the compute).  One JSON line on rank 0.
 
     python bench.py                       # N=1, C2 workload
+    python bench.py --dump-outputs DIR    # ... and a seeded sample of the last step's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N
 
 `--rows/--reads/--read-len` shrink the workload for rehearsals (the line then
@@ -32,6 +33,7 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 GATHER_CEILING_G = 39.5        # G random 32-byte rows (2 x 16 B loads, one line fill)/s this chip sustains on a 16 GiB table
 GATHER_CEILING_LINE_G = 47.0   # G random whole 128-byte lines/s, fetched lane-cooperatively into LDS, on a 128 GiB table
 ALG_BYTES_PER_BASE = 27
+DUMP_BASES = 1 << 22           # --dump-outputs: bases sampled over all ranks (two float32 arrays, 32 MiB)
 
 
 def parse():
@@ -48,7 +50,27 @@ def parse():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--gather", choices=("packed", "raw"), default="packed",
                     help="N > 1: PML values travel to rank 0 as one bit per base (gather codec) or as u16")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last step's PML values and col ids of a fixed sample "
+                         "of reads as DIR/pml.npy and DIR/cid.npy (float32, shape ranks x reads x read length)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def dump_outputs(path, pml, cid, n_reads, m):
+    """Writes whole reads of the (ranks, bases) result tensors -- the same reads of every rank, drawn
+    with a fixed seed -- as path/pml.npy and path/cid.npy; at most DUMP_BASES bases in all."""
+    import torch
+    world = pml.shape[0]
+    k = min(n_reads, max(1, DUMP_BASES // (world * m)))
+    reads = np.sort(np.random.default_rng(0).choice(n_reads, size=k, replace=False))
+    pos = torch.from_numpy((reads[:, None] * m + np.arange(m)).reshape(-1)).to(pml.device)
+    os.makedirs(path, exist_ok=True)
+    for name, arr, values in (("pml", pml, np.uint16), ("cid", cid, np.uint8)):
+        host = arr.index_select(1, pos).cpu().numpy().view(values)      # PML is u16 held in an int16 tensor
+        np.save(os.path.join(path, f"{name}.npy"), host.reshape(world, k, m).astype(np.float32))
 
 
 def main():
@@ -208,6 +230,16 @@ def main():
                 gather_ok = gather_ok and all(bool(torch.equal(got_c[r][lo:hi], rawc[r])) and bool(torch.equal(got_p[r][lo:hi], raw[r]))
                                               for r in range(world))
             del raw, rawc
+
+    # --dump-outputs (untimed): what the caller of the timed path holds after its last step, on rank 0:
+    # its own results for N = 1, every rank's gathered and rebuilt results for N > 1
+    if args.dump_outputs and rank == 0:
+        if world == 1:
+            res_p, res_c = d_pml[:n_bases].view(1, -1), d_cid[:n_bases].view(1, -1)
+        else:
+            res_p = g_pml if codecs else pipe.gathered[0].view(torch.int16)
+            res_c = g_cid if g_cid is not None else pipe.gathered[-1]
+        dump_outputs(args.dump_outputs, res_p, res_c, n_reads, m)
 
     kernel_ms = [a.elapsed_time(b) for a, b in kernel_events]
     launches = len(kernel_ms)

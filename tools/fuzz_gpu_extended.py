@@ -1,5 +1,5 @@
 import sys, os, time
-root = os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, "tests"))
 from __graft_entry__ import load_package, load_oracle
 import test_gpu_parity as t
