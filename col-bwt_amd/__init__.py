@@ -30,6 +30,7 @@ EXPORTS = (
     "colbwt_synth_reads_device", "colbwt_build_col_pml", "colbwt_build_col_pml_arrays",
     "colbwt_col_split", "colbwt_col_split_arrays", "colbwt_col_split_error",
     "colbwt_rlbwt_build_text", "colbwt_rlbwt_build_files", "colbwt_rlbwt_get", "colbwt_rlbwt_free", "colbwt_rlbwt_error",
+    "colbwt_count_batch", "colbwt_count_device", "colbwt_count_file",
 )
 
 
@@ -108,6 +109,9 @@ def lib():
     L.colbwt_synth_reads_device.argtypes = [vp, u64, C.c_uint32, C.c_uint32, u64, vp, vp, vp]
     L.colbwt_build_col_pml.argtypes = [C.c_char_p, C.c_char_p]
     L.colbwt_build_col_pml_arrays.argtypes = [vp, u64, vp, vp, u64, vp, u64, vp, u64, vp, u64, C.POINTER(u64)]
+    L.colbwt_count_batch.argtypes = [vp, vp, vp, u64, vp, vp, vp, C.POINTER(Stats)]
+    L.colbwt_count_device.argtypes = [vp, vp, vp, u64, u64, vp, vp, vp, vp, vp, C.POINTER(Stats)]
+    L.colbwt_count_file.argtypes = [vp, C.c_char_p, C.c_char_p, u64, C.POINTER(Stats)]
     _lib = L
     return L
 
@@ -212,6 +216,43 @@ class ColPml:
                                               os.fsencode(pml_bin_path) if pml_bin_path else None,
                                               os.fsencode(cid_bin_path) if cid_bin_path else None,
                                               batch_bases, C.byref(st)))
+        return st
+
+    # -- exact-match counting (backward search; include/colbwt.h colbwt_count_batch) --
+    def count_batch(self, bases, read_off, want_sp=False):
+        """Many reads -> (mlen uint32, occ uint64, sp uint64 or None, Stats), one entry per read:
+        mlen = length of the longest suffix of the read that occurs in the text, occ = its occurrences,
+        sp = its rank among the text's suffixes (want_sp)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        n_reads = max(read_off.size - 1, 0)
+        mlen = np.zeros(n_reads, np.uint32)
+        occ = np.zeros(n_reads, np.uint64)
+        sp = np.zeros(n_reads, np.uint64) if want_sp else None
+        st = Stats()
+        _check(lib().colbwt_count_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n_reads, mlen.ctypes.data,
+                                        occ.ctypes.data, sp.ctypes.data if want_sp else None, C.byref(st)))
+        return mlen, occ, sp, st
+
+    def count(self, pattern):
+        """One read -> (mlen, occ, sp) as ints."""
+        p = np.frombuffer(bytes(pattern), dtype=np.uint8)
+        mlen, occ, sp, _ = self.count_batch(p, np.array([0, p.size], np.uint64), want_sp=True)
+        return int(mlen[0]), int(occ[0]), int(sp[0])
+
+    def count_device(self, d_bases, d_read_off, n_reads, n_bases, d_mlen, d_occ, d_sp=None, d_order=None, stream=0,
+                     timed=False):
+        """Device-resident count entry point: raw device pointers (ints); d_sp / d_order may be None."""
+        st = Stats()
+        _check(lib().colbwt_count_device(self._h, d_bases, d_read_off, n_reads, n_bases, d_mlen, d_occ, d_sp, d_order,
+                                         stream, C.byref(st) if timed else None))
+        return st
+
+    def count_file(self, pattern_path, out_path=None, batch_bases=0):
+        """FASTA/FASTQ(.gz) -> text lines "name\tm\tmlen\tocc" (default <pattern>.count)."""
+        st = Stats()
+        _check(lib().colbwt_count_file(self._h, os.fsencode(pattern_path), os.fsencode(out_path) if out_path else None,
+                                       batch_bases, C.byref(st)))
         return st
 
     def cid_dictionary(self):

@@ -22,6 +22,7 @@
 
 #include "../../include/colbwt.h"
 #include "bin_writer.h"
+#include "count_query.h"
 #include "fasta_parallel.h"
 #include "fastx_reader.h"
 #include "index.h"
@@ -262,6 +263,23 @@ hipError_t staged_d2h(colbwt_index *idx, const D2HSegment *seg, int n_seg, hipSt
     return e != hipSuccess ? e : e2;
 }
 
+// Lane order of a ragged batch: the reads by decreasing length (a counting sort over 256 length
+// classes is enough: waves only need reads of SIMILAR length side by side).  Left empty when the
+// batch is small or even enough for the natural order.
+void length_order(const uint64_t *read_off, uint64_t n_reads, uint64_t max_len, uint64_t min_len,
+                  std::vector<uint32_t> &order) {
+    if (n_reads > 0xFFFFFFFFull || n_reads <= 64 || max_len <= min_len + (min_len >> 2) + 16) return;
+    const uint64_t span = max_len - min_len + 1;
+    uint32_t shift = 0;
+    while ((span >> shift) > 4096) ++shift;
+    std::vector<uint64_t> start((span >> shift) + 2, 0);
+    for (uint64_t k = 0; k < n_reads; ++k) ++start[((max_len - (read_off[k + 1] - read_off[k])) >> shift) + 1];
+    for (size_t b = 1; b < start.size(); ++b) start[b] += start[b - 1];
+    order.resize(n_reads);
+    for (uint64_t k = 0; k < n_reads; ++k)
+        order[start[(max_len - (read_off[k + 1] - read_off[k])) >> shift]++] = (uint32_t)k;
+}
+
 // One replica's part of a host-entry query: reads [0, n_reads) of `read_off`, whose offsets are
 // relative to `bases` after subtracting `off0` (a shard of a larger batch keeps the caller's
 // offsets).  Results go to pml / cid indexed like `bases`.
@@ -283,22 +301,10 @@ int query_batch_host(colbwt_index *idx, const uint8_t *bases, const uint64_t *re
     BatchScratch own;
     BatchScratch &S = lease.try_lock() ? idx->scratch : own;
 
-    // Ragged batch: assign lanes by decreasing read length (counting sort over 256 length
-    // classes is enough: waves only need reads of SIMILAR length side by side).  The line-row
-    // kernel balances by itself (persistent lanes claim chunks of reads).
+    // Ragged batch: assign lanes by decreasing read length.  The line-row kernel balances by
+    // itself (persistent lanes claim chunks of reads).
     std::vector<uint32_t> order;
-    if (!idx->ix.line_rows() && n_reads <= 0xFFFFFFFFull && n_reads > 64 &&
-        max_len > min_len + (min_len >> 2) + 16) {
-        const uint64_t span = max_len - min_len + 1;
-        uint32_t shift = 0;
-        while ((span >> shift) > 4096) ++shift;
-        std::vector<uint64_t> start((span >> shift) + 2, 0);
-        for (uint64_t k = 0; k < n_reads; ++k) ++start[((max_len - (read_off[k + 1] - read_off[k])) >> shift) + 1];
-        for (size_t b = 1; b < start.size(); ++b) start[b] += start[b - 1];
-        order.resize(n_reads);
-        for (uint64_t k = 0; k < n_reads; ++k)
-            order[start[(max_len - (read_off[k + 1] - read_off[k])) >> shift]++] = (uint32_t)k;
-    }
+    if (!idx->ix.line_rows()) length_order(read_off, n_reads, max_len, min_len, order);
     std::vector<uint64_t> rebased;                            // offsets from 0 for this shard
     const uint64_t *off_src = read_off;
     if (off0 != 0) {
@@ -452,6 +458,142 @@ int query_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *rea
             stats->n_bases += sts[r].n_bases;
             stats->algorithmic_bytes += sts[r].algorithmic_bytes;
             stats->h2d_ms = std::max(stats->h2d_ms, sts[r].h2d_ms);          // the devices work side by side
+            stats->kernel_ms = std::max(stats->kernel_ms, sts[r].kernel_ms);
+            stats->d2h_ms = std::max(stats->d2h_ms, sts[r].d2h_ms);
+        }
+    }
+    return COLBWT_OK;
+}
+
+// One replica's part of a host-entry count query (count_query.h): reads [0, n_reads) of
+// `read_off` (offsets relative to `bases` after subtracting `off0`), results per read.
+int count_batch_host(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t off0, uint64_t n_reads,
+                     uint32_t *mlen, uint64_t *occ, uint64_t *sp, uint64_t max_len, uint64_t min_len, colbwt_stats *stats,
+                     std::string &errmsg) {
+    auto bad = [&](int code, const std::string &m) { errmsg = m; return code; };
+    const uint64_t n_bases = read_off[n_reads] - off0;
+    if (stats) memset(stats, 0, sizeof(*stats));
+    int rc = select_device(idx->ix.device(), errmsg);
+    if (rc != COLBWT_OK) return rc;
+
+    std::unique_lock<std::mutex> lease(idx->scratch_mu, std::defer_lock);
+    BatchScratch own;
+    BatchScratch &S = lease.try_lock() ? idx->scratch : own;
+    std::vector<uint32_t> order;
+    length_order(read_off, n_reads, max_len, min_len, order);
+    std::vector<uint64_t> rebased;
+    const uint64_t *off_src = read_off;
+    if (off0 != 0) {
+        rebased.resize(n_reads + 1);
+        for (uint64_t k = 0; k <= n_reads; ++k) rebased[k] = read_off[k] - off0;
+        off_src = rebased.data();
+    }
+    const uint64_t bases_alloc = (n_bases + 64 + 63) & ~63ull;  // the kernel reads whole 64-byte blocks
+    float ms_h2d = 0, ms_k = 0, ms_d2h = 0;
+    hipStream_t stream = nullptr;
+#define COUNT_HIP(expr)                                                                         \
+    do {                                                                                        \
+        hipError_t e_ = (expr);                                                                 \
+        if (e_ != hipSuccess) {                                                                 \
+            (void)hipGetLastError();                                                            \
+            if (stream) (void)hipStreamSynchronize(stream);                                     \
+            return bad(e_ == hipErrorOutOfMemory ? COLBWT_ERR_NOMEM : COLBWT_ERR_HIP,           \
+                       std::string(#expr) + ": " + hipGetErrorString(e_));                      \
+        }                                                                                       \
+    } while (0)
+    COUNT_HIP(S.ready());
+    COUNT_HIP(S.need(0, bases_alloc));
+    COUNT_HIP(S.need(1, (n_reads + 1) * sizeof(uint64_t)));
+    COUNT_HIP(S.need(2, n_reads * sizeof(uint32_t)));
+    COUNT_HIP(S.need(3, 2 * n_reads * sizeof(uint64_t)));
+    if (!order.empty()) COUNT_HIP(S.need(4, n_reads * sizeof(uint32_t)));
+    stream = S.stream;
+    uint8_t *d_bases = (uint8_t *)S.buf[0];
+    uint64_t *d_off = (uint64_t *)S.buf[1];
+    uint32_t *d_mlen = (uint32_t *)S.buf[2];
+    uint64_t *d_occ = (uint64_t *)S.buf[3];
+    uint64_t *d_sp = sp ? d_occ + n_reads : nullptr;
+    uint32_t *d_order = order.empty() ? nullptr : (uint32_t *)S.buf[4];
+
+    COUNT_HIP(hipEventRecord(S.ev[0], stream));
+    COUNT_HIP(hipMemsetAsync(d_bases + (bases_alloc - 128), 0, 128, stream));
+    if (n_bases) COUNT_HIP(hipMemcpyAsync(d_bases, bases, n_bases, hipMemcpyHostToDevice, stream));
+    COUNT_HIP(hipMemcpyAsync(d_off, off_src, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
+    if (d_order) COUNT_HIP(hipMemcpyAsync(d_order, order.data(), n_reads * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    COUNT_HIP(hipEventRecord(S.ev[1], stream));
+    launch_count(idx->ix.layout(), idx->ix.table(), idx->ix.table_k(), idx->ix.table_fat(), d_bases, d_off, n_reads, d_mlen,
+                 d_occ, d_sp, d_order, stream);
+    COUNT_HIP(hipGetLastError());
+    COUNT_HIP(hipEventRecord(S.ev[2], stream));
+    COUNT_HIP(hipMemcpyAsync(mlen, d_mlen, n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    COUNT_HIP(hipMemcpyAsync(occ, d_occ, n_reads * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    if (sp) COUNT_HIP(hipMemcpyAsync(sp, d_sp, n_reads * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
+    COUNT_HIP(hipEventRecord(S.ev[3], stream));
+    COUNT_HIP(hipStreamSynchronize(stream));
+    COUNT_HIP(hipEventElapsedTime(&ms_h2d, S.ev[0], S.ev[1]));
+    COUNT_HIP(hipEventElapsedTime(&ms_k, S.ev[1], S.ev[2]));
+    COUNT_HIP(hipEventElapsedTime(&ms_d2h, S.ev[2], S.ev[3]));
+#undef COUNT_HIP
+    if (stats) {
+        stats->n_reads = n_reads;
+        stats->n_bases = n_bases;
+        stats->h2d_ms = ms_h2d;
+        stats->kernel_ms = ms_k;
+        stats->d2h_ms = ms_d2h;
+    }
+    return COLBWT_OK;
+}
+
+// Count queries for a batch in host memory over every replica of the handle: contiguous shards of
+// equal base count, side by side (as query_batch_all).
+int count_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t *mlen,
+                    uint64_t *occ, uint64_t *sp, colbwt_stats *stats) {
+    if (!idx) return fail(COLBWT_ERR_ARG, "null index");
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n_reads == 0) return COLBWT_OK;
+    if (!read_off) return fail(COLBWT_ERR_ARG, "null read_off");
+    if (read_off[0] != 0) return fail(COLBWT_ERR_ARG, "read_off[0] must be 0");
+    uint64_t max_len = 0, min_len = ~0ull;
+    for (uint64_t k = 0; k < n_reads; ++k) {
+        if (read_off[k + 1] < read_off[k]) return fail(COLBWT_ERR_ARG, "read_off not non-decreasing");
+        max_len = std::max(max_len, read_off[k + 1] - read_off[k]);
+        min_len = std::min(min_len, read_off[k + 1] - read_off[k]);
+    }
+    const uint64_t n_bases = read_off[n_reads];
+    if (max_len > 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, "read longer than 2^32-1 bases");
+    if ((n_bases && !bases) || !mlen || !occ) return fail(COLBWT_ERR_ARG, "null bases/mlen/occ");
+
+    std::vector<colbwt_index *> reps{idx};
+    reps.insert(reps.end(), idx->more.begin(), idx->more.end());
+    const size_t R = reps.size();
+    std::vector<uint64_t> cut(R + 1, 0);
+    cut[R] = n_reads;
+    for (size_t r = 1; r < R; ++r) {
+        const uint64_t target = n_bases / R * r + n_bases % R * r / R;
+        const uint64_t k = (uint64_t)(std::lower_bound(read_off, read_off + n_reads + 1, target) - read_off);
+        cut[r] = std::min(std::max(k, cut[r - 1]), n_reads);
+    }
+    std::vector<int> rcs(R, COLBWT_OK);
+    std::vector<std::string> msgs(R);
+    std::vector<colbwt_stats> sts(R);
+    auto work = [&](size_t r) {
+        const uint64_t lo = cut[r], hi = cut[r + 1];
+        if (hi == lo) return;
+        const uint64_t off0 = read_off[lo];
+        rcs[r] = count_batch_host(reps[r], bases + off0, read_off + lo, off0, hi - lo, mlen + lo, occ + lo, sp ? sp + lo : nullptr,
+                                  max_len, min_len, &sts[r], msgs[r]);
+    };
+    std::vector<std::thread> threads;
+    for (size_t r = 1; r < R; ++r) threads.emplace_back(work, r);
+    work(0);
+    for (auto &t : threads) t.join();
+    for (size_t r = 0; r < R; ++r)
+        if (rcs[r] != COLBWT_OK) return fail(rcs[r], "device " + std::to_string(reps[r]->ix.device()) + ": " + msgs[r]);
+    if (stats) {
+        for (size_t r = 0; r < R; ++r) {
+            stats->n_reads += sts[r].n_reads;
+            stats->n_bases += sts[r].n_bases;
+            stats->h2d_ms = std::max(stats->h2d_ms, sts[r].h2d_ms);
             stats->kernel_ms = std::max(stats->kernel_ms, sts[r].kernel_ms);
             stats->d2h_ms = std::max(stats->d2h_ms, sts[r].d2h_ms);
         }
@@ -741,9 +883,11 @@ done:
 // the calling thread runs the GPU query (on every replica of the handle), a writer thread lays
 // out and writes the two result files -- so the wall time is the slowest stage's, not the sum.
 // Output bytes and order are those of the sequential loop.  `binary`: the container of
-// bin_writer.h instead of the reference's text.
+// bin_writer.h instead of the reference's text.  `count`: count queries (count_query.h) instead,
+// one line per read "name\tm\tmlen\tocc\n" in pml_name (cid_name unused).
 static int query_file_impl(colbwt_index *idx, const char *pattern_path, const std::string &pml_name,
-                           const std::string &cid_name, uint64_t batch_bases, colbwt_stats *stats, bool binary) {
+                           const std::string &cid_name, uint64_t batch_bases, colbwt_stats *stats, bool binary,
+                           bool count = false) {
     if (stats) memset(stats, 0, sizeof(*stats));
     const size_t replicas = 1 + idx->more.size();
     if (batch_bases == 0) batch_bases = (64ull << 20) * replicas;
@@ -753,8 +897,16 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
     if (!parallel && !reader.open(pattern_path)) return fail(COLBWT_ERR_IO, std::string("cannot open pattern file ") + pattern_path);
     TextWriter wp, wc;
     BinWriter bp, bc;
-    if (!(binary ? bp.open(pml_name) : wp.open(pml_name))) return fail(COLBWT_ERR_IO, "cannot create " + pml_name);
-    if (!(binary ? bc.open(cid_name) : wc.open(cid_name))) return fail(COLBWT_ERR_IO, "cannot create " + cid_name);
+    FILE *wn = nullptr;
+    if (count) {
+        wn = fopen(pml_name.c_str(), "wb");
+        if (!wn) return fail(COLBWT_ERR_IO, "cannot create " + pml_name);
+        setvbuf(wn, nullptr, _IOFBF, 4u << 20);
+    } else {
+        if (!(binary ? bp.open(pml_name) : wp.open(pml_name))) return fail(COLBWT_ERR_IO, "cannot create " + pml_name);
+        if (!(binary ? bc.open(cid_name) : wc.open(cid_name))) return fail(COLBWT_ERR_IO, "cannot create " + cid_name);
+    }
+    bool count_ok = true;
 
     FileBatch pool[kFileBatches];
     std::unique_lock<std::mutex> pinned(idx->file_mu, std::defer_lock);
@@ -823,6 +975,16 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
             if (!b) break;
             const uint64_t n_reads = b->names.size();
             const double t0 = now();
+            if (count) {
+                const uint32_t *ml = b->pml->as<uint32_t>();
+                const uint64_t *oc = b->cid->as<uint64_t>();
+                for (uint64_t k = 0; k < n_reads && count_ok; ++k)
+                    count_ok = fprintf(wn, "%s\t%llu\t%u\t%llu\n", b->names[k].c_str(),
+                                       (unsigned long long)(b->off[k + 1] - b->off[k]), ml[k], (unsigned long long)oc[k]) > 0;
+                t_format += now() - t0;
+                free_q.push(b);
+                continue;
+            }
             // pml_query.cpp:78-85; the two files are laid out side by side, each by several
             // host threads (same bytes, same order as the sequential loop)
             std::thread cid_thread([&] {
@@ -855,9 +1017,14 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
         const double t0 = now();
         colbwt_stats st{};
         rc = select_device(idx->ix.device(), g_err);
-        if (rc == COLBWT_OK && (!b->cid->ensure(nb) || !b->pml->ensure(nb * (b->wide ? 4 : 2))))
+        if (rc == COLBWT_OK && count && (!b->pml->ensure(n_reads * 4) || !b->cid->ensure(n_reads * 8)))
+            rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
+        if (rc == COLBWT_OK && !count && (!b->cid->ensure(nb) || !b->pml->ensure(nb * (b->wide ? 4 : 2))))
             rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
         if (rc != COLBWT_OK) {
+        } else if (count) {
+            rc = count_batch_all(idx, b->bases.data(), b->off.data(), n_reads, b->pml->as<uint32_t>(), b->cid->as<uint64_t>(),
+                                 nullptr, &st);
         } else if (b->wide) {
             rc = colbwt_query_batch_u32(idx, b->bases.data(), b->off.data(), n_reads, b->pml->as<uint32_t>(),
                                         b->cid->as<uint8_t>(), &st);
@@ -884,7 +1051,8 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
     done_q.push(nullptr);
     reader_thread.join();
     writer_thread.join();
-    const bool okp = binary ? bp.close() : wp.close(), okc = binary ? bc.close() : wc.close();
+    const bool okp = count ? fclose(wn) == 0 && count_ok : binary ? bp.close() : wp.close();
+    const bool okc = count || (binary ? bc.close() : wc.close());
     if (trace)
         fprintf(stderr, "colbwt_query_file: wall %.3f s; busy: parse %.3f, gpu %.3f, layout+write %.3f\n",
                 now() - t_begin, t_parse, t_gpu, t_format);
@@ -907,6 +1075,56 @@ int colbwt_query_file_binary(colbwt_index *idx, const char *pattern_path, const 
     if (!idx || !pattern_path) return fail(COLBWT_ERR_ARG, "null argument");
     return query_file_impl(idx, pattern_path, pml_bin_path ? pml_bin_path : std::string(pattern_path) + ".pml.bin",
                            cid_bin_path ? cid_bin_path : std::string(pattern_path) + ".cid.bin", batch_bases, stats, true);
+}
+
+int colbwt_count_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t *mlen,
+                       uint64_t *occ, uint64_t *sp, colbwt_stats *stats) {
+    return count_batch_all(idx, bases, read_off, n_reads, mlen, occ, sp, stats);
+}
+
+int colbwt_count_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads,
+                        uint64_t n_bases, uint32_t *d_mlen, uint64_t *d_occ, uint64_t *d_sp, const uint32_t *d_order,
+                        void *hip_stream, colbwt_stats *stats) {
+    if (!idx) return fail(COLBWT_ERR_ARG, "null index");
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (n_reads == 0) return COLBWT_OK;
+    if (!d_bases || !d_read_off || !d_mlen || !d_occ) return fail(COLBWT_ERR_ARG, "null device pointer");
+    if (((uintptr_t)d_bases & 15) || ((uintptr_t)d_mlen & 3) || ((uintptr_t)d_occ & 7) || ((uintptr_t)d_sp & 7))
+        return fail(COLBWT_ERR_ARG, "d_bases must be 16-byte aligned, d_mlen 4-byte and d_occ/d_sp 8-byte aligned");
+    idx = replica_for(idx, d_bases);
+    int rc = select_device(idx->ix.device(), g_err);
+    if (rc != COLBWT_OK) return rc;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float ms = 0;
+    if (stats) {
+        API_HIP(hipEventCreate(&e0));
+        API_HIP(hipEventCreate(&e1));
+        API_HIP(hipEventRecord(e0, stream));
+    }
+    launch_count(idx->ix.layout(), idx->ix.table(), idx->ix.table_k(), idx->ix.table_fat(), d_bases, d_read_off, n_reads, d_mlen,
+                 d_occ, d_sp, d_order, stream);
+    API_HIP(hipGetLastError());
+    if (stats) {
+        API_HIP(hipEventRecord(e1, stream));
+        API_HIP(hipEventSynchronize(e1));
+        API_HIP(hipEventElapsedTime(&ms, e0, e1));
+        stats->n_reads = n_reads;
+        stats->n_bases = n_bases;
+        stats->kernel_ms = ms;
+    }
+    rc = COLBWT_OK;
+done:
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    return rc;
+}
+
+int colbwt_count_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint64_t batch_bases,
+                      colbwt_stats *stats) {
+    if (!idx || !pattern_path) return fail(COLBWT_ERR_ARG, "null argument");
+    const std::string out = out_path ? out_path : std::string(pattern_path) + ".count";
+    return query_file_impl(idx, pattern_path, out, out, batch_bases, stats, false, true);
 }
 
 int colbwt_binary_to_text(const char *bin_path, int value_bytes, const char *text_path) {

@@ -205,6 +205,37 @@ int colbwt_query_file_binary(colbwt_index *idx, const char *pattern_path, const 
  * .pml.bin, 1 for .cid.bin.  Host code. */
 int colbwt_binary_to_text(const char *bin_path, int value_bytes, const char *text_path);
 
+/* ---- exact-match counting (backward search) ----------------------------------------------
+ * How often does a read occur in the text, and how much of it?  Backward search over the same
+ * table: for read P[0..m), start with the whole BWT range [sp, ep] = [0, n-1] and for
+ * i = m-1 .. 0, c = P[i]: s = first position >= sp whose BWT character is c, e = last position
+ * <= ep holding c; c absent from the table or s > e ends the search; else sp = LF(s), ep = LF(e)
+ * (the move-structure step of the query above), and sp > ep afterwards (synthetic tables only)
+ * ends it too without consuming the base.  Read bytes are compared exactly as the query compares
+ * them.  Per read (not per base):
+ *   mlen  bases consumed = the length of the longest suffix of the read that occurs in the text
+ *         (mlen == m: the whole read occurs)
+ *   occ   ep - sp + 1 of the last non-empty range = the occurrences of that suffix; 0 when mlen == 0
+ *         (empty reads included)
+ *   sp    (nullable) the first position of that range = the suffix's rank among the text's
+ *         suffixes; 0 when mlen == 0
+ * Works on every layout; needs nothing beyond what the open put in HBM.  Arguments, error codes,
+ * stream and concurrency contract as colbwt_query_batch / colbwt_query_device_ordered: read k is
+ * bases[read_off[k] .. read_off[k+1]), reads up to 2^32-1 bases; the host form shards the reads
+ * over the replicas of a colbwt_index_open_devices handle.  Device form: d_bases 16-byte aligned
+ * with 64 readable bytes past read_off[n_reads], d_mlen 4-byte and d_occ / d_sp 8-byte aligned,
+ * d_order (nullable) assigns lanes as in colbwt_query_device_ordered (results identical). */
+int colbwt_count_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads,
+                       uint32_t *mlen, uint64_t *occ, uint64_t *sp, colbwt_stats *stats);
+int colbwt_count_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads,
+                        uint64_t n_bases, uint32_t *d_mlen, uint64_t *d_occ, uint64_t *d_sp, const uint32_t *d_order,
+                        void *hip_stream, colbwt_stats *stats);
+/* FASTA/FASTQ(.gz) in (the reader and batch pipeline of colbwt_query_file), one text line per read
+ * out: "name\tm\tmlen\tocc\n", name as colbwt_query_file prints it after '>'.  out_path NULL =>
+ * pattern + ".count". */
+int colbwt_count_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint64_t batch_bases,
+                      colbwt_stats *stats);
+
 /* ---- index construction (SURVEY.md 8(f) "next" #1) ------------------------ */
 
 /* build_col_bwt <prefix> (src/build_col_bwt.cpp:14-52): reads <prefix>.bwt.heads,
