@@ -259,3 +259,70 @@ def write_fasta(path, reads, names=None, width=60):
                 f.write(b[s:s + width] + b"\n")
             if not b:
                 f.write(b"\n")
+
+
+# ---- position-keyed hash of a result array (device-side comparisons of outputs too large to copy)
+_M64 = (1 << 64) - 1
+
+
+def _s64(x):
+    """An unsigned 64-bit constant as the int64 with the same bits (torch has no uint64 arithmetic)."""
+    x &= _M64
+    return x - (1 << 64) if x >> 63 else x
+
+
+_H_POS = _s64(0x9E3779B97F4A7C15)
+_H_VAL = _s64(0xD6E8FEB86659FD93)
+_H_M1 = _s64(0xBF58476D1CE4E5B9)
+_H_M2 = _s64(0x94D049BB133111EB)
+
+
+def _shr_logical(torch, x, s):
+    """x >> s as on uint64: torch's `>>` on int64 shifts the sign bit in."""
+    return torch.bitwise_and(torch.bitwise_right_shift(x, s), (1 << (64 - s)) - 1)
+
+
+def position_hash(values, extra=None, start=0, slice_elems=1 << 26):
+    """sum_k mix(start + k, values[k]) mod 2^64 (an int).  mix is splitmix64's finalizer of
+    (position + 1) * phi + value * c, so swapping two values, a +1 / -1 pair, or moving the data by
+    one position changes the hash, and the total does not depend on where the array is cut:
+    position_hash(v) == position_hash(v[:k]) + position_hash(v[k:], start=k) mod 2^64.
+    `values` is a 1-D torch integer tensor on any device; int16 / int32 elements count as their
+    unsigned bits (PML arrays).  `extra` (same length, e.g. the col ids) joins each value in the
+    bits above 32.  Hashed `slice_elems` elements at a time so the int64 temporaries stay small;
+    int64 products and sums wrap, so the arithmetic is mod 2^64."""
+    import torch
+    assert extra is None or extra.numel() == values.numel()
+    total = 0
+    for lo in range(0, values.numel(), slice_elems):
+        v = _unsigned64(torch, values[lo:lo + slice_elems])
+        if extra is not None:
+            v.bitwise_or_(_unsigned64(torch, extra[lo:lo + slice_elems]).bitwise_left_shift_(32))
+        x = torch.arange(start + lo + 1, start + lo + 1 + v.numel(), dtype=torch.int64, device=v.device)
+        x.mul_(_H_POS).add_(v.mul_(_H_VAL))
+        del v
+        for s, m in ((30, _H_M1), (27, _H_M2)):
+            x.bitwise_xor_(_shr_logical(torch, x, s)).mul_(m)
+        x.bitwise_xor_(_shr_logical(torch, x, 31))
+        total += int(x.sum().item())
+        del x
+    return total & _M64
+
+
+def _unsigned64(torch, t):
+    bits = {torch.int8: 0xFF, torch.int16: 0xFFFF, torch.int32: 0xFFFFFFFF}.get(t.dtype)
+    v = t.to(torch.int64, copy=True)                # a copy even of int64 input: it is changed in place
+    return v.bitwise_and_(bits) if bits is not None else v
+
+
+def position_hash_reference(values, extra=None, start=0):
+    """position_hash in Python integers (its definition; small inputs only).  Values are taken
+    modulo 2^16 / 2^32 by the caller's dtype: pass them already unsigned."""
+    total = 0
+    for k, v in enumerate(values):
+        v = int(v) | (int(extra[k]) << 32 if extra is not None else 0)
+        x = ((start + k + 1) * (_H_POS & _M64) + v * (_H_VAL & _M64)) & _M64
+        x = ((x ^ (x >> 30)) * (_H_M1 & _M64)) & _M64
+        x = ((x ^ (x >> 27)) * (_H_M2 & _M64)) & _M64
+        total += x ^ (x >> 31)
+    return total & _M64

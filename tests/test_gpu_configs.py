@@ -4,9 +4,11 @@ failure paths the capacity configuration depends on.
   C3  the per-rank shard of the 8-GPU run is the C2 batch (same index, 10 M x 150 bp per GPU):
       covered by test_gpu_parity.py::test_full_scale_properties and named here.
   C4  2e8-row index, >= 100 k reads of ~10 kbp (+-20 % length jitter, 5 % substitutions), all
-      four HBM layouts, device entry point with and without the length order, host entry point;
-      and the configuration's own size, 1 M reads (1e10 bases), on line rows: two runs and the
-      three-step layout compared on the device, the oracle on the first, middle and last reads.
+      six HBM layouts, device entry point with and without the length order, host entry point;
+      and the configuration's own size, 1 M reads (1e10 bases), on the layout AUTO takes (line
+      rows with deep mismatch lines): two runs, then plain mismatch lines and three-step rows,
+      compared by a position-keyed hash on the device; the oracle on the first, middle and last
+      reads.
   C5  capacity: the largest indices one MI355X takes -- 1e9 rows opened with AUTO (line rows do
       not fit, which the build finds out after one counting pass: three-step rows, ~130 GB resident), 1.7e9 rows where the three-step refinement passes 2^32-2 rows and
       AUTO must settle for two-step rows -- plus the HBM-budget fallback and what a failed open
@@ -74,7 +76,7 @@ def test_c4_long_reads_all_layouts(pkg, oracle, c2_image):
     ref = oracle.OracleIndex(c2_image)
     expect = None
     host_result = None
-    for layout in (4, 3, 2, 1):
+    for layout in (6, 5, 4, 3, 2, 1):                    # 6 first: the layout AUTO takes is the one the oracle checks
         _free_hbm()
         tbl = pkg.ColPml.from_bytes(c2_image, layout=layout)
         assert tbl.info().layout == layout
@@ -133,14 +135,16 @@ def test_c4_long_reads_all_layouts(pkg, oracle, c2_image):
 
 def test_c4_at_baseline_size_one_million_long_reads(pkg, oracle, c2_image):
     """BASELINE configs[3] at its own size: 1 M reads of 8-12 kbp (1e10 bases, 5 % substitutions,
-    backward walks on the 2e8-row index) on the layout AUTO picks (line rows with mismatch lines) --
-    five reads per persistent lane, so every
-    lane claims further chunks from its workgroup's counter and the last tenth of every share goes
-    out read by read (fat_query.hip ChunkPlan; the 100 k-read case above never gets there).
-    Two runs are compared ON THE DEVICE, then with the three-step layout's run on the same
-    buffers; the oracle (col_bwt.hpp:498-529 restated) checks >= 50 Mbase taken from the FIRST,
-    MIDDLE and LAST reads of the batch -- the tail is where single-read chunks are claimed."""
+    backward walks on the 2e8-row index) on the layout AUTO picks without a budget (line rows with
+    deep mismatch lines) -- five reads per persistent lane, so every lane claims further chunks from
+    its workgroup's counter and the last tenth of every share goes out read by read (fat_query.hip
+    ChunkPlan; the 100 k-read case above never gets there).  One result buffer pair is resident at a
+    time: each run is reduced to a position-keyed hash on the device (helpers.position_hash) and
+    freed.  The deep layout twice, then plain mismatch lines and three-step rows, must hash alike;
+    the oracle (col_bwt.hpp:498-529 restated) checks >= 50 Mbase of the first run taken from the
+    FIRST, MIDDLE and LAST reads of the batch -- the tail is where single-read chunks are claimed."""
     import torch
+    import helpers
     dev = torch.device("cuda", 0)
     n_reads = int(os.environ.get("COLBWT_TEST_C4_READS", "1000000"))
     m_max, chunk = 12_000, 20_000
@@ -150,15 +154,21 @@ def test_c4_at_baseline_size_one_million_long_reads(pkg, oracle, c2_image):
     off_np[1:] = np.cumsum(lens_np)
     nb = int(off_np[-1])
     _free_hbm()
-    # AUTO under a budget that keeps room for this batch (10 GB of bases, 30 GB of results, twice the
-    # results for the comparison): line rows with plain mismatch lines -- without the budget AUTO takes
-    # deep entries on this index (229 GB of 288) and the batch does not fit next to it
-    os.environ["COLBWT_HBM_BUDGET_MB"] = "230000"
-    try:
-        tbl = pkg.ColPml.from_bytes(c2_image, layout=0)
-    finally:
-        os.environ.pop("COLBWT_HBM_BUDGET_MB", None)
-    assert tbl.info().layout == 5
+    tbl = pkg.ColPml.from_bytes(c2_image, layout=0)
+    info = tbl.info()
+    if C2_ROWS == 200_000_000:
+        assert info.layout == 6, info.layout
+    print(f"C4 at BASELINE size: AUTO layout == {info.layout}, K = {info.layout_shape >> 8}, "
+          f"{info.device_bytes / 1e9:.1f} GB resident")
+    # what the batch needs next to the index: bases and offsets, then the larger of the read sampler's
+    # temporaries (a chunk of walks, its suffixes and two int64 index arrays per base) and one PML (u16)
+    # + col-id pair with guard bytes plus the hash's int64 temporaries (at most six of one slice)
+    synth = chunk * m_max * (1 + 1 + 8 + 8)
+    results = 3 * (nb + 64) + 6 * 8 * (1 << 26)
+    need = (nb + 128) + 8 * (n_reads + 1) + max(synth, results)
+    free = _free_hbm()
+    assert free > need + (1 << 30), f"{free / 1e9:.1f} GB of HBM free beside the index, the batch needs {need / 1e9:.1f} GB"
+    print(f"  HBM free beside the index {free / 1e9:.1f} GB, the batch needs {need / 1e9:.1f} GB")
     d_bases = torch.zeros(nb + 128, dtype=torch.uint8, device=dev)
     d_off = torch.from_numpy(off_np).to(dev)
     d_fixed = torch.zeros(chunk * m_max + 128, dtype=torch.uint8, device=dev)
@@ -172,38 +182,47 @@ def test_c4_at_baseline_size_one_million_long_reads(pkg, oracle, c2_image):
         del part, part_off
     del d_fixed, d_foff
     torch.cuda.synchronize()
+    ref = oracle.OracleIndex(c2_image)
 
-    def run(t):
+    def run(t, check_oracle=False):
+        """One run -> (hash of PML and col ids by position, kernel ms); the buffers are freed."""
         p = torch.full((nb + 64,), -1, dtype=torch.int16, device=dev)
         c = torch.full((nb + 64,), 0xEE, dtype=torch.uint8, device=dev)
         st = t.query_device(d_bases.data_ptr(), d_off.data_ptr(), n_reads, nb, p.data_ptr(), c.data_ptr(), 2, 0, timed=True)
         assert (p[nb:] == -1).all() and (c[nb:] == 0xEE).all()           # nothing written past the batch
-        return p[:nb], c[:nb], st.kernel_ms
-    p1, c1, ms1 = run(tbl)
-    p2, c2, _ = run(tbl)
-    assert torch.equal(p1, p2) and torch.equal(c1, c2)
-    del p2, c2
-    print(f"C4 at BASELINE size: {n_reads} reads, {nb} bases, line rows + mismatch lines {ms1:.1f} ms = {nb / ms1 / 1e6:.1f} Gbase/s")
-    # the oracle on the first, middle and last reads
-    ref = oracle.OracleIndex(c2_image)
-    per = max(1, min(n_reads // 3, 1_800))
-    checked = 0
-    for lo in (0, (n_reads - per) // 2, n_reads - per):
-        b0, b1 = int(off_np[lo]), int(off_np[lo + per])
-        ep, ec = ref.query_batch(d_bases[b0:b1].cpu().numpy(), (off_np[lo:lo + per + 1] - b0).astype(np.uint64), threads=16)
-        assert np.array_equal(p1[b0:b1].cpu().numpy().view(np.uint16), ep), f"PML differs from the oracle in reads {lo}.."
-        assert np.array_equal(c1[b0:b1].cpu().numpy(), ec), f"col ids differ from the oracle in reads {lo}.."
-        assert 0.05 < float((ep == 0).mean()) < 0.7
-        checked += b1 - b0
-    assert checked >= min(50_000_000, nb * 0.9)
+        if check_oracle:                                                 # the oracle on the first, middle and last reads
+            per = max(1, min(n_reads // 3, 1_800))
+            checked = 0
+            for lo in (0, (n_reads - per) // 2, n_reads - per):
+                b0, b1 = int(off_np[lo]), int(off_np[lo + per])
+                ep, ec = ref.query_batch(d_bases[b0:b1].cpu().numpy(), (off_np[lo:lo + per + 1] - b0).astype(np.uint64), threads=16)
+                assert np.array_equal(p[b0:b1].cpu().numpy().view(np.uint16), ep), f"PML differs from the oracle in reads {lo}.."
+                assert np.array_equal(c[b0:b1].cpu().numpy(), ec), f"col ids differ from the oracle in reads {lo}.."
+                assert 0.05 < float((ep == 0).mean()) < 0.7
+                checked += b1 - b0
+            assert checked >= min(50_000_000, nb * 0.9)
+            # the device hash of a slice equals the host hash of the same slice (int64 wrap-around on both)
+            b0 = int(off_np[n_reads // 2])
+            b1 = min(nb, b0 + 1_000_003)
+            assert helpers.position_hash(p[b0:b1], c[b0:b1], start=b0) == \
+                helpers.position_hash(p[b0:b1].cpu(), c[b0:b1].cpu(), start=b0)
+        h = helpers.position_hash(p[:nb], c[:nb])
+        del p, c
+        _free_hbm()
+        return h, st.kernel_ms
+    h1, ms1 = run(tbl, check_oracle=True)
+    print(f"  layout {info.layout}: {n_reads} reads, {nb} bases, {ms1:.1f} ms = {nb / ms1 / 1e6:.1f} Gbase/s")
+    h2, _ = run(tbl)
+    assert h1 == h2, "two runs of the deep layout differ"
     tbl.close()
-    _free_hbm()
-    tbl3 = pkg.ColPml.from_bytes(c2_image, layout=3)
-    assert tbl3.info().layout == 3
-    p3, c3, ms3 = run(tbl3)
-    assert torch.equal(p1, p3) and torch.equal(c1, c3), "three-step rows and line rows disagree"
-    print(f"  three-step rows {ms3:.1f} ms = {nb / ms3 / 1e6:.1f} Gbase/s")
-    tbl3.close()
+    for layout, name in ((5, "line rows + mismatch lines"), (3, "three-step rows")):
+        _free_hbm()
+        t = pkg.ColPml.from_bytes(c2_image, layout=layout)
+        assert t.info().layout == layout
+        h, ms = run(t)
+        print(f"  layout {layout} ({name}): {ms:.1f} ms = {nb / ms / 1e6:.1f} Gbase/s")
+        assert h == h1, f"layout {layout} and layout {info.layout} disagree"
+        t.close()
 
 
 def _oracle_sample_check(pkg, oracle_index, tbl, n_reads, m, seed, sample):

@@ -6,7 +6,8 @@
 Each variant loads the same synthetic index, runs the query on the same
 device-resident reads (sampled once), interleaved `reps` times; prints one JSON
 line per variant with the HIP-event kernel time and a checksum of the outputs
-(all variants must agree).
+(all variants must agree): tests/helpers.position_hash of the PML and of the col-id array, which a
+permutation, a +1 / -1 pair or a shift changes (plain sums do not see them).
 """
 import argparse
 import ctypes as C
@@ -18,7 +19,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 from __graft_entry__ import load_package  # noqa: E402
+from helpers import position_hash  # noqa: E402
 
 
 class Stats(C.Structure):
@@ -87,9 +90,8 @@ def main():
             if rep:
                 times.append(st.kernel_ms)
             else:
-                step = 1 << 28                      # in slices: an int64 copy of 1e10 values would not fit beside the index
-                sums[name] = (sum(int(d_pml[a:min(a + step, nb)].to(torch.int64).sum().item()) for a in range(0, nb, step)),
-                              sum(int(d_cid[a:min(a + step, nb)].to(torch.int64).sum().item()) for a in range(0, nb, step)))
+                # hashed in slices: an int64 copy of 1e10 values would not fit beside the index
+                sums[name] = (position_hash(d_pml[:nb]), position_hash(d_cid[:nb]))
             del d_pml, d_cid
     ref = sums[variants[0][0]]
     # a checksum only says something when there is another variant to compare with: with a single
@@ -99,7 +101,7 @@ def main():
                           "Gbase_s": round(nb / np.mean(times) / 1e6, 3),
                           "checksum_ok": (sums[name] == ref) if len(variants) > 1 else None,
                           "checksum_against": variants[0][0] if len(variants) > 1 and k else None,
-                          "checksum": list(sums[name]),   # sums of all PML values / col ids: comparable across processes
+                          "checksum": [f"{h:016x}" for h in sums[name]],   # position hashes of PML / col ids: comparable across processes
                           "index": shape, "rows": a.rows, "reads": n_reads, "read_len": m, "pml_bytes": a.pml_bytes}), flush=True)
 
 
