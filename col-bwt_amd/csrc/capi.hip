@@ -41,7 +41,7 @@ constexpr int kDefaultLineSteps = 8;
 struct BatchScratch {
     hipStream_t stream = nullptr;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    void *buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // bases, offsets, pml, cid, order
+    void *buf[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};   // bases, offsets, two result arrays, order
     size_t cap[5] = {0, 0, 0, 0, 0};
     ~BatchScratch() { release(); }
     void release() {
@@ -140,14 +140,26 @@ int fail(int code, const std::string &msg) {
     return code;
 }
 
-#define API_HIP(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) {                                                               \
-            rc = fail(e_ == hipErrorOutOfMemory ? COLBWT_ERR_NOMEM : COLBWT_ERR_HIP,          \
-                      std::string(#expr) + ": " + hipGetErrorString(e_));                     \
-            goto done;                                                                        \
-        }                                                                                     \
+// A failed HIP call `what`: its colbwt code, with "<what>: <HIP's message>" in `msg`.  Whatever the
+// call queued on `stream` (nullptr: none of ours) is drained first: nothing of it may still be
+// running when the caller gets its arrays (and the next caller the staging buffers) back.
+int hip_failed(hipError_t e, const char *what, hipStream_t stream, std::string &msg) {
+    (void)hipGetLastError();
+    if (stream) (void)hipStreamSynchronize(stream);
+    msg = std::string(what) + ": " + hipGetErrorString(e);
+    return e == hipErrorOutOfMemory ? COLBWT_ERR_NOMEM : COLBWT_ERR_HIP;
+}
+
+// The launch an entry point just made: COLBWT_ERR_HIP with "<entry>: <HIP's message>" when it failed.
+int launch_status(const char *entry) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? COLBWT_OK : fail(COLBWT_ERR_HIP, std::string(entry) + ": " + hipGetErrorString(e));
+}
+
+#define TRY_HIP(expr, stream, msg)                                                    \
+    do {                                                                              \
+        const hipError_t e_ = (expr);                                                 \
+        if (e_ != hipSuccess) return hip_failed(e_, #expr, stream, msg);              \
     } while (0)
 
 bool widths_ok(const colbwt_widths *w) {
@@ -158,11 +170,16 @@ struct MappedFile {
     const uint8_t *data = nullptr;
     uint64_t len = 0;
     int fd = -1;
-    ~MappedFile() {
+    ~MappedFile() { close(); }
+    void close() {
         if (data && len) munmap((void *)data, len);
-        if (fd >= 0) close(fd);
+        if (fd >= 0) ::close(fd);
+        data = nullptr;
+        len = 0;
+        fd = -1;
     }
     bool open(const std::string &path) {
+        close();
         fd = ::open(path.c_str(), O_RDONLY);
         if (fd < 0) return false;
         struct stat st;
@@ -175,6 +192,13 @@ struct MappedFile {
         return true;
     }
 };
+
+// The index file of an open by name: prefix + ".col_pml" (pml_query.cpp:110-111, col_bwt.hpp:434-437),
+// else the path itself.
+int map_index_file(const char *prefix_or_file, MappedFile &mf) {
+    if (mf.open(std::string(prefix_or_file) + ".col_pml") || mf.open(prefix_or_file)) return COLBWT_OK;
+    return fail(COLBWT_ERR_IO, std::string("cannot open ") + prefix_or_file + ".col_pml (or " + prefix_or_file + ")");
+}
 
 constexpr size_t kStageBytes = 128u << 20;     // per staging buffer
 constexpr size_t kStageMinTotal = 256u << 20;  // smaller results: the plain copy is as good
@@ -280,31 +304,60 @@ void length_order(const uint64_t *read_off, uint64_t n_reads, uint64_t max_len, 
         order[start[(max_len - (read_off[k + 1] - read_off[k])) >> shift]++] = (uint32_t)k;
 }
 
-// One replica's part of a host-entry query: reads [0, n_reads) of `read_off`, whose offsets are
+// The three layout-dependent choices of a query: each is made here and nowhere else.
+// Whether the PML kernel of the layout assigns lanes by d_order: the one- and two-step rows do;
+// three-step rows (sk3_query.hip) and line rows have persistent lanes that balance by themselves.
+bool pml_reads_order(const Index &ix) { return ix.layout() <= 2; }
+
+void launch_query(const Index &ix, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads, uint64_t n_bases,
+                  void *d_pml, int pml_bytes, uint8_t *d_cid, const uint32_t *d_order, hipStream_t stream) {
+    if (ix.line_rows())
+        launch_fat_query(ix.table_fat(), d_bases, d_read_off, n_reads, n_bases, d_pml, pml_bytes, d_cid, d_order, stream);
+    else if (ix.layout() >= 2)
+        launch_sk_query(ix.table_k(), d_bases, d_read_off, n_reads, n_bases, d_pml, pml_bytes, d_cid, d_order, stream);
+    else
+        launch_pml_query(ix.table(), d_bases, d_read_off, n_reads, d_pml, pml_bytes, d_cid, d_order, stream);
+}
+
+void launch_sampler(const Index &ix, uint64_t n_reads, uint32_t read_len, uint32_t sub_permille, uint64_t seed,
+                    uint8_t *d_bases, uint64_t *d_read_off, hipStream_t stream) {
+    if (ix.line_rows())
+        launch_fat_synth_reads(ix.table_fat(), n_reads, read_len, sub_permille, seed, d_bases, d_read_off, stream);
+    else if (ix.layout() >= 2)   // the one-step tables are gone once the K-step rows exist
+        launch_sk_synth_reads(ix.table_k(), n_reads, read_len, sub_permille, seed, d_bases, d_read_off, stream);
+    else
+        launch_synth_reads(ix.table(), n_reads, read_len, sub_permille, seed, d_bases, d_read_off, stream);
+}
+
+// One replica's batch in HBM, in the buffers of a BatchScratch: what a caller's launch and fetch see.
+struct DeviceBatch {
+    uint8_t *bases;
+    uint64_t *off;
+    uint32_t *order;   // nullptr: lanes in read order
+    void *out[2];      // the caller's two result arrays
+    hipStream_t stream;
+};
+
+// One replica's part of a host-entry batch: reads [0, n_reads) of `read_off`, whose offsets are
 // relative to `bases` after subtracting `off0` (a shard of a larger batch keeps the caller's
-// offsets).  Results go to pml / cid indexed like `bases`.
-template <typename PmlT>
-int query_batch_host(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t off0, uint64_t n_reads,
-                     PmlT *pml, uint8_t *cid, uint64_t max_len, uint64_t min_len, colbwt_stats *stats, std::string &errmsg) {
-    auto bad = [&](int code, const std::string &m) { errmsg = m; return code; };
+// offsets).  The replica's scratch (or, when another caller holds it, one for this call) takes the
+// bases, the rebased offsets, the lane order of a ragged batch (when `ordered`) and two result
+// arrays of out_bytes[0] / out_bytes[1] bytes; then `launch(batch)` enqueues the kernel and
+// `fetch(batch)` copies the results back (a colbwt code; HIP failures through TRY_HIP).
+template <typename Launch, typename Fetch>
+int replica_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t off0, uint64_t n_reads,
+                  uint64_t max_len, uint64_t min_len, bool ordered, const uint64_t out_bytes[2], uint64_t alg_bytes_per_base,
+                  colbwt_stats *stats, std::string &msg, Launch launch, Fetch fetch) {
     const uint64_t n_bases = read_off[n_reads] - off0;
     if (stats) memset(stats, 0, sizeof(*stats));
-    if (n_bases == 0) {
-        if (stats) stats->n_reads = n_reads;
-        return COLBWT_OK;
-    }
-    int rc = select_device(idx->ix.device(), errmsg);
+    int rc = select_device(idx->ix.device(), msg);
     if (rc != COLBWT_OK) return rc;
 
-    // the handle's scratch when nobody else holds it, else one for this call
     std::unique_lock<std::mutex> lease(idx->scratch_mu, std::defer_lock);
     BatchScratch own;
     BatchScratch &S = lease.try_lock() ? idx->scratch : own;
-
-    // Ragged batch: assign lanes by decreasing read length.  The line-row kernel balances by
-    // itself (persistent lanes claim chunks of reads).
-    std::vector<uint32_t> order;
-    if (!idx->ix.line_rows()) length_order(read_off, n_reads, max_len, min_len, order);
+    std::vector<uint32_t> order;   // ragged batch: lanes by decreasing read length
+    if (ordered) length_order(read_off, n_reads, max_len, min_len, order);
     std::vector<uint64_t> rebased;                            // offsets from 0 for this shard
     const uint64_t *off_src = read_off;
     if (off0 != 0) {
@@ -313,92 +366,56 @@ int query_batch_host(colbwt_index *idx, const uint8_t *bases, const uint64_t *re
         off_src = rebased.data();
     }
     const uint64_t bases_alloc = (n_bases + 64 + 63) & ~63ull;  // the kernel reads whole 64-byte blocks
-    float ms_h2d = 0, ms_k = 0, ms_d2h = 0;
-    uint8_t *d_bases = nullptr, *d_cid = nullptr;
-    uint64_t *d_off = nullptr;
-    uint32_t *d_order = nullptr;
-    PmlT *d_pml = nullptr;
+    const uint64_t tail = std::min<uint64_t>(bases_alloc, 128);   // zeroed past the bases
     hipStream_t stream = nullptr;
-#define HOST_HIP(expr)                                                                          \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) {                                                                 \
-            (void)hipGetLastError();                                                            \
-            /* nothing of this call may still be running when the caller gets its arrays (and the \
-               next caller the staging buffers) back: kernel and copies are drained first */      \
-            if (stream) (void)hipStreamSynchronize(stream);                                     \
-            return bad(e_ == hipErrorOutOfMemory ? COLBWT_ERR_NOMEM : COLBWT_ERR_HIP,           \
-                       std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-        }                                                                                       \
-    } while (0)
-    HOST_HIP(S.ready());
-    HOST_HIP(S.need(0, bases_alloc));
-    HOST_HIP(S.need(1, (n_reads + 1) * sizeof(uint64_t)));
-    HOST_HIP(S.need(2, ((n_bases + 15) & ~15ull) * sizeof(PmlT)));
-    HOST_HIP(S.need(3, (n_bases + 15) & ~15ull));
-    if (!order.empty()) HOST_HIP(S.need(4, n_reads * sizeof(uint32_t)));
+    TRY_HIP(S.ready(), stream, msg);
+    TRY_HIP(S.need(0, bases_alloc), stream, msg);
+    TRY_HIP(S.need(1, (n_reads + 1) * sizeof(uint64_t)), stream, msg);
+    TRY_HIP(S.need(2, out_bytes[0]), stream, msg);
+    TRY_HIP(S.need(3, out_bytes[1]), stream, msg);
+    if (!order.empty()) TRY_HIP(S.need(4, n_reads * sizeof(uint32_t)), stream, msg);
     stream = S.stream;
-    d_bases = (uint8_t *)S.buf[0];
-    d_off = (uint64_t *)S.buf[1];
-    d_pml = (PmlT *)S.buf[2];
-    d_cid = (uint8_t *)S.buf[3];
-    d_order = order.empty() ? nullptr : (uint32_t *)S.buf[4];
+    const DeviceBatch b{(uint8_t *)S.buf[0], (uint64_t *)S.buf[1], order.empty() ? nullptr : (uint32_t *)S.buf[4],
+                        {S.buf[2], S.buf[3]}, stream};
 
-    HOST_HIP(hipEventRecord(S.ev[0], stream));
-    HOST_HIP(hipMemsetAsync(d_bases + (bases_alloc - 128), 0, 128, stream));
-    HOST_HIP(hipMemcpyAsync(d_bases, bases, n_bases, hipMemcpyHostToDevice, stream));
-    HOST_HIP(hipMemcpyAsync(d_off, off_src, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-    if (d_order) HOST_HIP(hipMemcpyAsync(d_order, order.data(), n_reads * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    HOST_HIP(hipEventRecord(S.ev[1], stream));
-    if (idx->ix.line_rows())
-        launch_fat_query(idx->ix.table_fat(), d_bases, d_off, n_reads, n_bases, d_pml, (int)sizeof(PmlT), d_cid, d_order, stream);
-    else if (idx->ix.layout() >= 2)
-        launch_sk_query(idx->ix.table_k(), d_bases, d_off, n_reads, n_bases, d_pml, (int)sizeof(PmlT), d_cid, d_order, stream);
-    else
-        launch_pml_query(idx->ix.table(), d_bases, d_off, n_reads, d_pml, (int)sizeof(PmlT), d_cid, d_order, stream);
-    HOST_HIP(hipGetLastError());
-    HOST_HIP(hipEventRecord(S.ev[2], stream));
-    {
-        // results into pageable memory go through pinned staging buffers with several copier
-        // threads (the runtime's own pageable path manages ~17 GB/s); pinned destinations and
-        // small batches are copied directly
-        std::unique_lock<std::mutex> stage_lock(idx->stage_mu, std::defer_lock);
-        const bool staged = n_bases * (sizeof(PmlT) + 1) >= kStageMinTotal && is_pageable(pml) && is_pageable(cid) &&
-                            stage_lock.try_lock() && ensure_stage(idx);
-        if (staged) {
-            const D2HSegment seg[2] = {{(uint8_t *)pml, (const uint8_t *)d_pml, n_bases * sizeof(PmlT)},
-                                       {cid, d_cid, n_bases}};
-            HOST_HIP(staged_d2h(idx, seg, 2, stream));
-        } else {
-            HOST_HIP(hipMemcpyAsync(pml, d_pml, n_bases * sizeof(PmlT), hipMemcpyDeviceToHost, stream));
-            HOST_HIP(hipMemcpyAsync(cid, d_cid, n_bases, hipMemcpyDeviceToHost, stream));
-        }
-    }
-    HOST_HIP(hipEventRecord(S.ev[3], stream));
-    HOST_HIP(hipStreamSynchronize(stream));
-    HOST_HIP(hipEventElapsedTime(&ms_h2d, S.ev[0], S.ev[1]));
-    HOST_HIP(hipEventElapsedTime(&ms_k, S.ev[1], S.ev[2]));
-    HOST_HIP(hipEventElapsedTime(&ms_d2h, S.ev[2], S.ev[3]));
-#undef HOST_HIP
+    TRY_HIP(hipEventRecord(S.ev[0], stream), stream, msg);
+    TRY_HIP(hipMemsetAsync(b.bases + (bases_alloc - tail), 0, tail, stream), stream, msg);
+    if (n_bases) TRY_HIP(hipMemcpyAsync(b.bases, bases, n_bases, hipMemcpyHostToDevice, stream), stream, msg);
+    TRY_HIP(hipMemcpyAsync(b.off, off_src, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream), stream, msg);
+    if (b.order)
+        TRY_HIP(hipMemcpyAsync(b.order, order.data(), n_reads * sizeof(uint32_t), hipMemcpyHostToDevice, stream), stream, msg);
+    TRY_HIP(hipEventRecord(S.ev[1], stream), stream, msg);
+    launch(b);
+    TRY_HIP(hipGetLastError(), stream, msg);
+    TRY_HIP(hipEventRecord(S.ev[2], stream), stream, msg);
+    rc = fetch(b);
+    if (rc != COLBWT_OK) return rc;
+    TRY_HIP(hipEventRecord(S.ev[3], stream), stream, msg);
+    TRY_HIP(hipStreamSynchronize(stream), stream, msg);
+    float ms[3] = {0, 0, 0};
+    for (int k = 0; k < 3; ++k) TRY_HIP(hipEventElapsedTime(&ms[k], S.ev[k], S.ev[k + 1]), stream, msg);
     if (stats) {
         stats->n_reads = n_reads;
         stats->n_bases = n_bases;
-        stats->h2d_ms = ms_h2d;
-        stats->kernel_ms = ms_k;
-        stats->d2h_ms = ms_d2h;
-        stats->algorithmic_bytes = n_bases * (uint64_t)kAlgBytesPerBase;
+        stats->h2d_ms = ms[0];
+        stats->kernel_ms = ms[1];
+        stats->d2h_ms = ms[2];
+        stats->algorithmic_bytes = n_bases * alg_bytes_per_base;
     }
     return COLBWT_OK;
 }
 
-// col_pml::query_pml for a batch in host memory, over every replica of the handle: the reads are
-// independent (the reference walks them one after the other, pml_query.cpp:74-86), so the batch
-// is cut into contiguous shards of equal base count, one per device, each queried by a host
-// thread of its own on its device's stream and copied straight into its slice of the caller's
-// arrays -- no exchange between devices.
-template <typename PmlT>
-int query_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, PmlT *pml,
-                    uint8_t *cid, colbwt_stats *stats) {
+// A batch in host memory over every replica of the handle: the reads are independent (the
+// reference walks them one after the other, pml_query.cpp:74-86), so the batch is cut into
+// contiguous shards of equal base count, one per replica, each run by
+// `part(replica, lo, hi, max_len, min_len, stats, msg)` on a host thread of its own (the first on the
+// calling thread) on its device's stream -- no exchange between devices.  Checks `read_off`, reads
+// longer than `max_read_len` (message `too_long`) and, through `bad_pointers(n_bases)`, the caller's
+// pointers.  Counts and bytes of the shards add up, times are the longest shard's.  A failure names
+// its device when there are several replicas, or when `name_device`.
+template <typename PointerCheck, typename Part>
+int sharded_batch(colbwt_index *idx, const uint64_t *read_off, uint64_t n_reads, uint64_t max_read_len, const char *too_long,
+                  bool name_device, colbwt_stats *stats, PointerCheck bad_pointers, Part part) {
     if (!idx) return fail(COLBWT_ERR_ARG, "null index");
     if (stats) memset(stats, 0, sizeof(*stats));
     if (n_reads == 0) return COLBWT_OK;
@@ -411,23 +428,12 @@ int query_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *rea
         min_len = std::min(min_len, read_off[k + 1] - read_off[k]);
     }
     const uint64_t n_bases = read_off[n_reads];
-    if (sizeof(PmlT) == 2 && max_len > 65535)
-        return fail(COLBWT_ERR_ARG, "read longer than 65535 bases: use colbwt_query_batch_u32");
-    if (max_len > 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, "read longer than 2^32-1 bases");
-    if (n_bases == 0) {
-        if (stats) stats->n_reads = n_reads;
-        return COLBWT_OK;
-    }
-    if (!bases || !pml || !cid) return fail(COLBWT_ERR_ARG, "null bases/pml/cid");
+    if (max_len > max_read_len) return fail(COLBWT_ERR_ARG, too_long);
+    if (const char *m = bad_pointers(n_bases)) return fail(COLBWT_ERR_ARG, m);
 
     std::vector<colbwt_index *> reps{idx};
     reps.insert(reps.end(), idx->more.begin(), idx->more.end());
     const size_t R = reps.size();
-    if (R == 1) {
-        std::string msg;
-        const int rc = query_batch_host<PmlT>(idx, bases, read_off, 0, n_reads, pml, cid, max_len, min_len, stats, msg);
-        return rc == COLBWT_OK ? rc : fail(rc, msg);
-    }
     // shard boundaries by base count (same rule as multi_gpu.shard_reads)
     std::vector<uint64_t> cut(R + 1, 0);
     cut[R] = n_reads;
@@ -440,18 +446,15 @@ int query_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *rea
     std::vector<std::string> msgs(R);
     std::vector<colbwt_stats> sts(R);
     auto work = [&](size_t r) {
-        const uint64_t lo = cut[r], hi = cut[r + 1];
-        if (hi == lo) return;
-        const uint64_t off0 = read_off[lo];
-        rcs[r] = query_batch_host<PmlT>(reps[r], bases + off0, read_off + lo, off0, hi - lo, pml + off0, cid + off0, max_len,
-                                        min_len, &sts[r], msgs[r]);
+        if (cut[r + 1] > cut[r]) rcs[r] = part(reps[r], cut[r], cut[r + 1], max_len, min_len, &sts[r], msgs[r]);
     };
     std::vector<std::thread> threads;
     for (size_t r = 1; r < R; ++r) threads.emplace_back(work, r);
     work(0);
     for (auto &t : threads) t.join();
     for (size_t r = 0; r < R; ++r)
-        if (rcs[r] != COLBWT_OK) return fail(rcs[r], "device " + std::to_string(reps[r]->ix.device()) + ": " + msgs[r]);
+        if (rcs[r] != COLBWT_OK)
+            return fail(rcs[r], R > 1 || name_device ? "device " + std::to_string(reps[r]->ix.device()) + ": " + msgs[r] : msgs[r]);
     if (stats) {
         for (size_t r = 0; r < R; ++r) {
             stats->n_reads += sts[r].n_reads;
@@ -465,140 +468,81 @@ int query_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *rea
     return COLBWT_OK;
 }
 
-// One replica's part of a host-entry count query (count_query.h): reads [0, n_reads) of
-// `read_off` (offsets relative to `bases` after subtracting `off0`), results per read.
-int count_batch_host(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t off0, uint64_t n_reads,
-                     uint32_t *mlen, uint64_t *occ, uint64_t *sp, uint64_t max_len, uint64_t min_len, colbwt_stats *stats,
-                     std::string &errmsg) {
-    auto bad = [&](int code, const std::string &m) { errmsg = m; return code; };
-    const uint64_t n_bases = read_off[n_reads] - off0;
-    if (stats) memset(stats, 0, sizeof(*stats));
-    int rc = select_device(idx->ix.device(), errmsg);
-    if (rc != COLBWT_OK) return rc;
-
-    std::unique_lock<std::mutex> lease(idx->scratch_mu, std::defer_lock);
-    BatchScratch own;
-    BatchScratch &S = lease.try_lock() ? idx->scratch : own;
-    std::vector<uint32_t> order;
-    length_order(read_off, n_reads, max_len, min_len, order);
-    std::vector<uint64_t> rebased;
-    const uint64_t *off_src = read_off;
-    if (off0 != 0) {
-        rebased.resize(n_reads + 1);
-        for (uint64_t k = 0; k <= n_reads; ++k) rebased[k] = read_off[k] - off0;
-        off_src = rebased.data();
-    }
-    const uint64_t bases_alloc = (n_bases + 64 + 63) & ~63ull;  // the kernel reads whole 64-byte blocks
-    float ms_h2d = 0, ms_k = 0, ms_d2h = 0;
-    hipStream_t stream = nullptr;
-#define COUNT_HIP(expr)                                                                         \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) {                                                                 \
-            (void)hipGetLastError();                                                            \
-            if (stream) (void)hipStreamSynchronize(stream);                                     \
-            return bad(e_ == hipErrorOutOfMemory ? COLBWT_ERR_NOMEM : COLBWT_ERR_HIP,           \
-                       std::string(#expr) + ": " + hipGetErrorString(e_));                      \
-        }                                                                                       \
-    } while (0)
-    COUNT_HIP(S.ready());
-    COUNT_HIP(S.need(0, bases_alloc));
-    COUNT_HIP(S.need(1, (n_reads + 1) * sizeof(uint64_t)));
-    COUNT_HIP(S.need(2, n_reads * sizeof(uint32_t)));
-    COUNT_HIP(S.need(3, 2 * n_reads * sizeof(uint64_t)));
-    if (!order.empty()) COUNT_HIP(S.need(4, n_reads * sizeof(uint32_t)));
-    stream = S.stream;
-    uint8_t *d_bases = (uint8_t *)S.buf[0];
-    uint64_t *d_off = (uint64_t *)S.buf[1];
-    uint32_t *d_mlen = (uint32_t *)S.buf[2];
-    uint64_t *d_occ = (uint64_t *)S.buf[3];
-    uint64_t *d_sp = sp ? d_occ + n_reads : nullptr;
-    uint32_t *d_order = order.empty() ? nullptr : (uint32_t *)S.buf[4];
-
-    COUNT_HIP(hipEventRecord(S.ev[0], stream));
-    COUNT_HIP(hipMemsetAsync(d_bases + (bases_alloc - 128), 0, 128, stream));
-    if (n_bases) COUNT_HIP(hipMemcpyAsync(d_bases, bases, n_bases, hipMemcpyHostToDevice, stream));
-    COUNT_HIP(hipMemcpyAsync(d_off, off_src, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, stream));
-    if (d_order) COUNT_HIP(hipMemcpyAsync(d_order, order.data(), n_reads * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-    COUNT_HIP(hipEventRecord(S.ev[1], stream));
-    launch_count(idx->ix.layout(), idx->ix.table(), idx->ix.table_k(), idx->ix.table_fat(), d_bases, d_off, n_reads, d_mlen,
-                 d_occ, d_sp, d_order, stream);
-    COUNT_HIP(hipGetLastError());
-    COUNT_HIP(hipEventRecord(S.ev[2], stream));
-    COUNT_HIP(hipMemcpyAsync(mlen, d_mlen, n_reads * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-    COUNT_HIP(hipMemcpyAsync(occ, d_occ, n_reads * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    if (sp) COUNT_HIP(hipMemcpyAsync(sp, d_sp, n_reads * sizeof(uint64_t), hipMemcpyDeviceToHost, stream));
-    COUNT_HIP(hipEventRecord(S.ev[3], stream));
-    COUNT_HIP(hipStreamSynchronize(stream));
-    COUNT_HIP(hipEventElapsedTime(&ms_h2d, S.ev[0], S.ev[1]));
-    COUNT_HIP(hipEventElapsedTime(&ms_k, S.ev[1], S.ev[2]));
-    COUNT_HIP(hipEventElapsedTime(&ms_d2h, S.ev[2], S.ev[3]));
-#undef COUNT_HIP
-    if (stats) {
-        stats->n_reads = n_reads;
-        stats->n_bases = n_bases;
-        stats->h2d_ms = ms_h2d;
-        stats->kernel_ms = ms_k;
-        stats->d2h_ms = ms_d2h;
-    }
-    return COLBWT_OK;
+// col_pml::query_pml for a batch in host memory: results per base, copied straight into each
+// shard's slice of the caller's arrays.
+template <typename PmlT>
+int query_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, PmlT *pml,
+                    uint8_t *cid, colbwt_stats *stats) {
+    const bool u16 = sizeof(PmlT) == 2;
+    auto bad_pointers = [&](uint64_t n_bases) -> const char * {
+        return n_bases && (!bases || !pml || !cid) ? "null bases/pml/cid" : nullptr;
+    };
+    auto part = [&](colbwt_index *rep, uint64_t lo, uint64_t hi, uint64_t max_len, uint64_t min_len, colbwt_stats *st,
+                    std::string &msg) {
+        const uint64_t off0 = read_off[lo], n_bases = read_off[hi] - off0;
+        if (n_bases == 0) {                                   // nothing to compute
+            st->n_reads = hi - lo;
+            return COLBWT_OK;
+        }
+        const uint64_t out_bytes[2] = {((n_bases + 15) & ~15ull) * sizeof(PmlT), (n_bases + 15) & ~15ull};
+        auto launch = [&](const DeviceBatch &b) {
+            launch_query(rep->ix, b.bases, b.off, hi - lo, n_bases, b.out[0], (int)sizeof(PmlT), (uint8_t *)b.out[1], b.order,
+                         b.stream);
+        };
+        auto fetch = [&](const DeviceBatch &b) {
+            PmlT *const p = pml + off0;
+            uint8_t *const c = cid + off0;
+            // results into pageable memory go through pinned staging buffers with several copier
+            // threads (the runtime's own pageable path manages ~17 GB/s); pinned destinations and
+            // small batches are copied directly
+            std::unique_lock<std::mutex> stage_lock(rep->stage_mu, std::defer_lock);
+            const bool staged = n_bases * (sizeof(PmlT) + 1) >= kStageMinTotal && is_pageable(p) && is_pageable(c) &&
+                                stage_lock.try_lock() && ensure_stage(rep);
+            if (staged) {
+                const D2HSegment seg[2] = {{(uint8_t *)p, (const uint8_t *)b.out[0], n_bases * sizeof(PmlT)},
+                                           {c, (const uint8_t *)b.out[1], n_bases}};
+                TRY_HIP(staged_d2h(rep, seg, 2, b.stream), b.stream, msg);
+            } else {
+                TRY_HIP(hipMemcpyAsync(p, b.out[0], n_bases * sizeof(PmlT), hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+                TRY_HIP(hipMemcpyAsync(c, b.out[1], n_bases, hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            }
+            return COLBWT_OK;
+        };
+        return replica_batch(rep, bases + off0, read_off + lo, off0, hi - lo, max_len, min_len, pml_reads_order(rep->ix),
+                             out_bytes, kAlgBytesPerBase, st, msg, launch, fetch);
+    };
+    return sharded_batch(idx, read_off, n_reads, u16 ? 65535 : 0xFFFFFFFFull,
+                         u16 ? "read longer than 65535 bases: use colbwt_query_batch_u32" : "read longer than 2^32-1 bases",
+                         false, stats, bad_pointers, part);
 }
 
-// Count queries for a batch in host memory over every replica of the handle: contiguous shards of
-// equal base count, side by side (as query_batch_all).
+// Count queries (count_query.h) for a batch in host memory: results per read.  The count kernel
+// assigns lanes by d_order on every layout (one lane per read).
 int count_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t *mlen,
                     uint64_t *occ, uint64_t *sp, colbwt_stats *stats) {
-    if (!idx) return fail(COLBWT_ERR_ARG, "null index");
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (n_reads == 0) return COLBWT_OK;
-    if (!read_off) return fail(COLBWT_ERR_ARG, "null read_off");
-    if (read_off[0] != 0) return fail(COLBWT_ERR_ARG, "read_off[0] must be 0");
-    uint64_t max_len = 0, min_len = ~0ull;
-    for (uint64_t k = 0; k < n_reads; ++k) {
-        if (read_off[k + 1] < read_off[k]) return fail(COLBWT_ERR_ARG, "read_off not non-decreasing");
-        max_len = std::max(max_len, read_off[k + 1] - read_off[k]);
-        min_len = std::min(min_len, read_off[k + 1] - read_off[k]);
-    }
-    const uint64_t n_bases = read_off[n_reads];
-    if (max_len > 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, "read longer than 2^32-1 bases");
-    if ((n_bases && !bases) || !mlen || !occ) return fail(COLBWT_ERR_ARG, "null bases/mlen/occ");
-
-    std::vector<colbwt_index *> reps{idx};
-    reps.insert(reps.end(), idx->more.begin(), idx->more.end());
-    const size_t R = reps.size();
-    std::vector<uint64_t> cut(R + 1, 0);
-    cut[R] = n_reads;
-    for (size_t r = 1; r < R; ++r) {
-        const uint64_t target = n_bases / R * r + n_bases % R * r / R;
-        const uint64_t k = (uint64_t)(std::lower_bound(read_off, read_off + n_reads + 1, target) - read_off);
-        cut[r] = std::min(std::max(k, cut[r - 1]), n_reads);
-    }
-    std::vector<int> rcs(R, COLBWT_OK);
-    std::vector<std::string> msgs(R);
-    std::vector<colbwt_stats> sts(R);
-    auto work = [&](size_t r) {
-        const uint64_t lo = cut[r], hi = cut[r + 1];
-        if (hi == lo) return;
-        const uint64_t off0 = read_off[lo];
-        rcs[r] = count_batch_host(reps[r], bases + off0, read_off + lo, off0, hi - lo, mlen + lo, occ + lo, sp ? sp + lo : nullptr,
-                                  max_len, min_len, &sts[r], msgs[r]);
+    auto bad_pointers = [&](uint64_t n_bases) -> const char * {
+        return (n_bases && !bases) || !mlen || !occ ? "null bases/mlen/occ" : nullptr;
     };
-    std::vector<std::thread> threads;
-    for (size_t r = 1; r < R; ++r) threads.emplace_back(work, r);
-    work(0);
-    for (auto &t : threads) t.join();
-    for (size_t r = 0; r < R; ++r)
-        if (rcs[r] != COLBWT_OK) return fail(rcs[r], "device " + std::to_string(reps[r]->ix.device()) + ": " + msgs[r]);
-    if (stats) {
-        for (size_t r = 0; r < R; ++r) {
-            stats->n_reads += sts[r].n_reads;
-            stats->n_bases += sts[r].n_bases;
-            stats->h2d_ms = std::max(stats->h2d_ms, sts[r].h2d_ms);
-            stats->kernel_ms = std::max(stats->kernel_ms, sts[r].kernel_ms);
-            stats->d2h_ms = std::max(stats->d2h_ms, sts[r].d2h_ms);
-        }
-    }
-    return COLBWT_OK;
+    auto part = [&](colbwt_index *rep, uint64_t lo, uint64_t hi, uint64_t max_len, uint64_t min_len, colbwt_stats *st,
+                    std::string &msg) {
+        const uint64_t n = hi - lo, off0 = read_off[lo];
+        const uint64_t out_bytes[2] = {n * sizeof(uint32_t), 2 * n * sizeof(uint64_t)};   // mlen; occ, then sp
+        auto launch = [&](const DeviceBatch &b) {
+            uint64_t *d_occ = (uint64_t *)b.out[1];
+            launch_count(rep->ix, b.bases, b.off, n, (uint32_t *)b.out[0], d_occ, sp ? d_occ + n : nullptr, b.order, b.stream);
+        };
+        auto fetch = [&](const DeviceBatch &b) {
+            const uint64_t *d_occ = (const uint64_t *)b.out[1];
+            TRY_HIP(hipMemcpyAsync(mlen + lo, b.out[0], n * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            TRY_HIP(hipMemcpyAsync(occ + lo, d_occ, n * sizeof(uint64_t), hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            if (sp) TRY_HIP(hipMemcpyAsync(sp + lo, d_occ + n, n * sizeof(uint64_t), hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            return COLBWT_OK;
+        };
+        return replica_batch(rep, bases + off0, read_off + lo, off0, n, max_len, min_len, true, out_bytes, 0, st, msg, launch,
+                             fetch);
+    };
+    return sharded_batch(idx, read_off, n_reads, 0xFFFFFFFFull, "read longer than 2^32-1 bases", true, stats, bad_pointers,
+                         part);
 }
 
 }  // namespace
@@ -652,6 +596,47 @@ static colbwt_index *replica_for(colbwt_index *idx, const void *d_ptr) {
     for (colbwt_index *r : idx->more)
         if (r->ix.device() == a.device) return r;
     return idx;
+}
+
+// The skeleton of a device entry point: `bad_argument()` names the first bad argument (after the
+// index; any pointer is fine when there are no reads), then `launch(ix, stream)` runs on the replica
+// on d_bases's device.  With `stats`, the launch is timed by two events and waited for.
+template <typename ArgCheck, typename Launch>
+static int device_entry(colbwt_index *idx, const void *d_bases, uint64_t n_reads, uint64_t n_bases, void *hip_stream,
+                        uint64_t alg_bytes_per_base, colbwt_stats *stats, ArgCheck bad_argument, Launch launch) {
+    if (!idx) return fail(COLBWT_ERR_ARG, "null index");
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (const char *m = bad_argument()) return fail(COLBWT_ERR_ARG, m);
+    if (n_reads == 0) return COLBWT_OK;
+    idx = replica_for(idx, d_bases);
+    const int rc = select_device(idx->ix.device(), g_err);
+    if (rc != COLBWT_OK) return rc;
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    struct Events {
+        hipEvent_t e[2] = {nullptr, nullptr};
+        ~Events() {
+            for (hipEvent_t x : e)
+                if (x) (void)hipEventDestroy(x);
+        }
+    } ev;
+    if (stats) {
+        TRY_HIP(hipEventCreate(&ev.e[0]), nullptr, g_err);
+        TRY_HIP(hipEventCreate(&ev.e[1]), nullptr, g_err);
+        TRY_HIP(hipEventRecord(ev.e[0], stream), nullptr, g_err);
+    }
+    launch(idx->ix, stream);
+    TRY_HIP(hipGetLastError(), nullptr, g_err);
+    if (stats) {
+        float ms = 0;
+        TRY_HIP(hipEventRecord(ev.e[1], stream), nullptr, g_err);
+        TRY_HIP(hipEventSynchronize(ev.e[1]), nullptr, g_err);
+        TRY_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]), nullptr, g_err);
+        stats->n_reads = n_reads;
+        stats->n_bases = n_bases;
+        stats->kernel_ms = ms;
+        stats->algorithmic_bytes = n_bases * alg_bytes_per_base;
+    }
+    return COLBWT_OK;
 }
 
 extern "C" {
@@ -743,17 +728,9 @@ int colbwt_index_open_layout(const char *prefix_or_file, const colbwt_widths *wi
                              colbwt_index **out) {
     if (!prefix_or_file || !out) return fail(COLBWT_ERR_ARG, "null argument");
     *out = nullptr;
-    // pml_query.cpp:110-111: filename = prefix + ".col_pml" (col_bwt.hpp:434-437)
     MappedFile mf;
-    std::string path = std::string(prefix_or_file) + ".col_pml";
-    if (!mf.open(path)) {
-        MappedFile direct;
-        path = prefix_or_file;
-        if (!direct.open(path))
-            return fail(COLBWT_ERR_IO, std::string("cannot open ") + prefix_or_file + ".col_pml (or " + prefix_or_file + ")");
-        return colbwt_index_open_memory_layout(direct.data, direct.len, widths, device, layout, out);
-    }
-    return colbwt_index_open_memory_layout(mf.data, mf.len, widths, device, layout, out);
+    const int rc = map_index_file(prefix_or_file, mf);
+    return rc != COLBWT_OK ? rc : colbwt_index_open_memory_layout(mf.data, mf.len, widths, device, layout, out);
 }
 
 // The same table on several devices (the replacement's open takes the devices to
@@ -789,14 +766,9 @@ int colbwt_index_open_devices(const char *prefix_or_file, const colbwt_widths *w
                               int layout, colbwt_index **out) {
     if (!prefix_or_file || !out) return fail(COLBWT_ERR_ARG, "null argument");
     *out = nullptr;
-    MappedFile mf;                                            // pml_query.cpp:110-111, as colbwt_index_open_layout
-    if (!mf.open(std::string(prefix_or_file) + ".col_pml")) {
-        MappedFile direct;
-        if (!direct.open(prefix_or_file))
-            return fail(COLBWT_ERR_IO, std::string("cannot open ") + prefix_or_file + ".col_pml (or " + prefix_or_file + ")");
-        return colbwt_index_open_memory_devices(direct.data, direct.len, widths, devices, n_devices, layout, out);
-    }
-    return colbwt_index_open_memory_devices(mf.data, mf.len, widths, devices, n_devices, layout, out);
+    MappedFile mf;
+    const int rc = map_index_file(prefix_or_file, mf);
+    return rc != COLBWT_OK ? rc : colbwt_index_open_memory_devices(mf.data, mf.len, widths, devices, n_devices, layout, out);
 }
 
 void colbwt_index_close(colbwt_index *idx) { delete idx; }
@@ -837,45 +809,18 @@ int colbwt_query_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_
 int colbwt_query_device_ordered(colbwt_index *idx, const uint8_t *d_bases, const uint64_t *d_read_off,
                                 uint64_t n_reads, uint64_t n_bases, void *d_pml, int pml_bytes, uint8_t *d_cid,
                                 const uint32_t *d_order, void *hip_stream, colbwt_stats *stats) {
-    if (!idx) return fail(COLBWT_ERR_ARG, "null index");
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (pml_bytes != 2 && pml_bytes != 4) return fail(COLBWT_ERR_ARG, "pml_bytes must be 2 or 4");
-    if (n_reads == 0) return COLBWT_OK;
-    if (!d_bases || !d_read_off || !d_pml || !d_cid) return fail(COLBWT_ERR_ARG, "null device pointer");
-    if (((uintptr_t)d_bases & 15) || ((uintptr_t)d_pml & 31) || ((uintptr_t)d_cid & 15))
-        return fail(COLBWT_ERR_ARG, "d_bases/d_cid must be 16-byte aligned and d_pml 32-byte aligned");
-    idx = replica_for(idx, d_bases);
-    int rc = select_device(idx->ix.device(), g_err);
-    if (rc != COLBWT_OK) return rc;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float ms = 0;
-    if (stats) {
-        API_HIP(hipEventCreate(&e0));
-        API_HIP(hipEventCreate(&e1));
-        API_HIP(hipEventRecord(e0, stream));
-    }
-    if (idx->ix.line_rows())
-        launch_fat_query(idx->ix.table_fat(), d_bases, d_read_off, n_reads, n_bases, d_pml, pml_bytes, d_cid, d_order, stream);
-    else if (idx->ix.layout() >= 2)
-        launch_sk_query(idx->ix.table_k(), d_bases, d_read_off, n_reads, n_bases, d_pml, pml_bytes, d_cid, d_order, stream);
-    else
-        launch_pml_query(idx->ix.table(), d_bases, d_read_off, n_reads, d_pml, pml_bytes, d_cid, d_order, stream);
-    API_HIP(hipGetLastError());
-    if (stats) {
-        API_HIP(hipEventRecord(e1, stream));
-        API_HIP(hipEventSynchronize(e1));
-        API_HIP(hipEventElapsedTime(&ms, e0, e1));
-        stats->n_reads = n_reads;
-        stats->n_bases = n_bases;
-        stats->kernel_ms = ms;
-        stats->algorithmic_bytes = n_bases * (uint64_t)kAlgBytesPerBase;
-    }
-    rc = COLBWT_OK;
-done:
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
+    auto bad_argument = [&]() -> const char * {
+        if (pml_bytes != 2 && pml_bytes != 4) return "pml_bytes must be 2 or 4";
+        if (n_reads == 0) return nullptr;
+        if (!d_bases || !d_read_off || !d_pml || !d_cid) return "null device pointer";
+        if (((uintptr_t)d_bases & 15) || ((uintptr_t)d_pml & 31) || ((uintptr_t)d_cid & 15))
+            return "d_bases/d_cid must be 16-byte aligned and d_pml 32-byte aligned";
+        return nullptr;
+    };
+    return device_entry(idx, d_bases, n_reads, n_bases, hip_stream, kAlgBytesPerBase, stats, bad_argument,
+                        [&](const Index &ix, hipStream_t stream) {
+                            launch_query(ix, d_bases, d_read_off, n_reads, n_bases, d_pml, pml_bytes, d_cid, d_order, stream);
+                        });
 }
 
 // pml_query vec mode (pml_query.cpp:92-143) as a three-stage pipeline over batches of reads:
@@ -1085,39 +1030,17 @@ int colbwt_count_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *
 int colbwt_count_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads,
                         uint64_t n_bases, uint32_t *d_mlen, uint64_t *d_occ, uint64_t *d_sp, const uint32_t *d_order,
                         void *hip_stream, colbwt_stats *stats) {
-    if (!idx) return fail(COLBWT_ERR_ARG, "null index");
-    if (stats) memset(stats, 0, sizeof(*stats));
-    if (n_reads == 0) return COLBWT_OK;
-    if (!d_bases || !d_read_off || !d_mlen || !d_occ) return fail(COLBWT_ERR_ARG, "null device pointer");
-    if (((uintptr_t)d_bases & 15) || ((uintptr_t)d_mlen & 3) || ((uintptr_t)d_occ & 7) || ((uintptr_t)d_sp & 7))
-        return fail(COLBWT_ERR_ARG, "d_bases must be 16-byte aligned, d_mlen 4-byte and d_occ/d_sp 8-byte aligned");
-    idx = replica_for(idx, d_bases);
-    int rc = select_device(idx->ix.device(), g_err);
-    if (rc != COLBWT_OK) return rc;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float ms = 0;
-    if (stats) {
-        API_HIP(hipEventCreate(&e0));
-        API_HIP(hipEventCreate(&e1));
-        API_HIP(hipEventRecord(e0, stream));
-    }
-    launch_count(idx->ix.layout(), idx->ix.table(), idx->ix.table_k(), idx->ix.table_fat(), d_bases, d_read_off, n_reads, d_mlen,
-                 d_occ, d_sp, d_order, stream);
-    API_HIP(hipGetLastError());
-    if (stats) {
-        API_HIP(hipEventRecord(e1, stream));
-        API_HIP(hipEventSynchronize(e1));
-        API_HIP(hipEventElapsedTime(&ms, e0, e1));
-        stats->n_reads = n_reads;
-        stats->n_bases = n_bases;
-        stats->kernel_ms = ms;
-    }
-    rc = COLBWT_OK;
-done:
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    return rc;
+    auto bad_argument = [&]() -> const char * {
+        if (n_reads == 0) return nullptr;
+        if (!d_bases || !d_read_off || !d_mlen || !d_occ) return "null device pointer";
+        if (((uintptr_t)d_bases & 15) || ((uintptr_t)d_mlen & 3) || ((uintptr_t)d_occ & 7) || ((uintptr_t)d_sp & 7))
+            return "d_bases must be 16-byte aligned, d_mlen 4-byte and d_occ/d_sp 8-byte aligned";
+        return nullptr;
+    };
+    return device_entry(idx, d_bases, n_reads, n_bases, hip_stream, 0, stats, bad_argument,
+                        [&](const Index &ix, hipStream_t stream) {
+                            launch_count(ix, d_bases, d_read_off, n_reads, d_mlen, d_occ, d_sp, d_order, stream);
+                        });
 }
 
 int colbwt_count_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint64_t batch_bases,
@@ -1138,21 +1061,13 @@ int colbwt_pml_pack_device(const uint16_t *d_pml, uint64_t n_bases, uint32_t *d_
     if (!d_pml || !d_mask) return fail(COLBWT_ERR_ARG, "null argument");
     if ((uintptr_t)d_pml % 32 || (uintptr_t)d_mask % 4) return fail(COLBWT_ERR_ARG, "d_pml must be 32-byte aligned");
     launch_pml_pack(d_pml, n_bases, d_mask, (hipStream_t)hip_stream);
-    {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(COLBWT_ERR_HIP, std::string("colbwt_pml_pack_device: ") + hipGetErrorString(e));
-    }
-    return COLBWT_OK;
+    return launch_status(__func__);
 }
 
 int colbwt_read_end_mask_device(const uint64_t *d_read_off, uint64_t n_reads, uint32_t *d_mask, void *hip_stream) {
     if (!d_read_off || !d_mask) return fail(COLBWT_ERR_ARG, "null argument");
     launch_read_end_mask(d_read_off, n_reads, d_mask, (hipStream_t)hip_stream);
-    {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(COLBWT_ERR_HIP, std::string("colbwt_read_end_mask_device: ") + hipGetErrorString(e));
-    }
-    return COLBWT_OK;
+    return launch_status(__func__);
 }
 
 int colbwt_pml_unpack_device(const uint32_t *d_zero_mask, const uint32_t *d_end_mask, uint64_t first_word,
@@ -1161,11 +1076,7 @@ int colbwt_pml_unpack_device(const uint32_t *d_zero_mask, const uint32_t *d_end_
     if (first_word + n_words > total_words) return fail(COLBWT_ERR_ARG, "word range beyond the masks");
     if ((uintptr_t)d_pml % 64) return fail(COLBWT_ERR_ARG, "d_pml must be 64-byte aligned");
     launch_pml_unpack(d_zero_mask, d_end_mask, first_word, n_words, total_words, d_pml, (hipStream_t)hip_stream);
-    {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(COLBWT_ERR_HIP, std::string("colbwt_pml_unpack_device: ") + hipGetErrorString(e));
-    }
-    return COLBWT_OK;
+    return launch_status(__func__);
 }
 
 int colbwt_index_cid_dictionary(const colbwt_index *idx, uint8_t *ids, uint32_t *n_ids) {
@@ -1194,9 +1105,7 @@ int colbwt_cid_pack_device(const uint8_t *d_cid, uint64_t n_bases, const uint8_t
     memset(code_of.v, 0, sizeof(code_of.v));
     for (uint32_t k = 0; k < n_ids; ++k) code_of.v[ids[k]] = (uint8_t)k;
     launch_cid_pack(d_cid, n_bases, code_of, cid_code_bits(n_ids), d_planes, (hipStream_t)hip_stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(COLBWT_ERR_HIP, std::string("colbwt_cid_pack_device: ") + hipGetErrorString(e));
-    return COLBWT_OK;
+    return launch_status(__func__);
 }
 
 int colbwt_cid_unpack_device(const uint32_t *d_planes, uint64_t first_word, uint64_t n_words, const uint8_t *ids, uint32_t n_ids,
@@ -1208,9 +1117,7 @@ int colbwt_cid_unpack_device(const uint32_t *d_planes, uint64_t first_word, uint
     memset(id_of.v, 0, sizeof(id_of.v));
     for (uint32_t k = 0; k < n_ids; ++k) id_of.v[k] = ids[k];
     launch_cid_unpack(d_planes, first_word, n_words, id_of, cid_code_bits(n_ids), d_cid, (hipStream_t)hip_stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(COLBWT_ERR_HIP, std::string("colbwt_cid_unpack_device: ") + hipGetErrorString(e));
-    return COLBWT_OK;
+    return launch_status(__func__);
 }
 
 int colbwt_synth_reads_device(colbwt_index *idx, uint64_t n_reads, uint32_t read_len, uint32_t sub_permille,
@@ -1220,17 +1127,10 @@ int colbwt_synth_reads_device(colbwt_index *idx, uint64_t n_reads, uint32_t read
     int rc = select_device(idx->ix.device(), g_err);
     if (rc != COLBWT_OK) return rc;
     hipStream_t stream = (hipStream_t)hip_stream;
-    API_HIP(hipMemsetAsync(d_bases + n_reads * (uint64_t)read_len, 0, 64, stream));
-    if (idx->ix.line_rows())
-        launch_fat_synth_reads(idx->ix.table_fat(), n_reads, read_len, sub_permille, seed, d_bases, d_read_off, stream);
-    else if (idx->ix.layout() >= 2)   // the one-step tables are gone once the K-step rows exist
-        launch_sk_synth_reads(idx->ix.table_k(), n_reads, read_len, sub_permille, seed, d_bases, d_read_off, stream);
-    else
-        launch_synth_reads(idx->ix.table(), n_reads, read_len, sub_permille, seed, d_bases, d_read_off, stream);
-    API_HIP(hipGetLastError());
-    rc = COLBWT_OK;
-done:
-    return rc;
+    TRY_HIP(hipMemsetAsync(d_bases + n_reads * (uint64_t)read_len, 0, 64, stream), nullptr, g_err);
+    launch_sampler(idx->ix, n_reads, read_len, sub_permille, seed, d_bases, d_read_off, stream);
+    TRY_HIP(hipGetLastError(), nullptr, g_err);
+    return COLBWT_OK;
 }
 
 }  // extern "C"

@@ -29,6 +29,7 @@
 
 #include "device_layout.h"
 #include "fat_layout.h"
+#include "index.h"
 #include "lane_io.h"
 #include "lf_device.h"
 #include "query_kernels.h"
@@ -223,25 +224,26 @@ __global__ __launch_bounds__(kQueryBlock) void count_kernel(V view, const uint8_
     if (sp_out) sp_out[rd] = sp;
 }
 
-// Count queries over whatever layout the index holds (exactly one of the tables is live).
-// layout: Index::layout() (1 one-step, 2 / 3 K-step, 4..6 line rows).
-inline void launch_count(int layout, const DevTable &T1, const SKTable &TK, const FatTable &TF, const uint8_t *d_bases,
-                         const uint64_t *d_read_off, uint64_t n_reads, uint32_t *d_mlen, uint64_t *d_occ, uint64_t *d_sp,
-                         const uint32_t *d_order, hipStream_t stream) {
-    if (n_reads == 0) return;
+template <typename View>
+inline void launch_count_view(const View &view, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads,
+                              uint32_t *d_mlen, uint64_t *d_occ, uint64_t *d_sp, const uint32_t *d_order, hipStream_t stream) {
     const dim3 grid((uint32_t)((n_reads + kQueryBlock - 1) / kQueryBlock)), block(kQueryBlock);
-    if (layout >= 4)
-        hipLaunchKernelGGL(count_kernel<CountFatView>, grid, block, 0, stream, CountFatView{TF}, d_bases, d_read_off, n_reads,
-                           d_mlen, d_occ, d_sp, d_order);
-    else if (layout == 3)
-        hipLaunchKernelGGL(count_kernel<CountSKView<3>>, grid, block, 0, stream, CountSKView<3>{TK}, d_bases, d_read_off,
-                           n_reads, d_mlen, d_occ, d_sp, d_order);
-    else if (layout == 2)
-        hipLaunchKernelGGL(count_kernel<CountSKView<2>>, grid, block, 0, stream, CountSKView<2>{TK}, d_bases, d_read_off,
-                           n_reads, d_mlen, d_occ, d_sp, d_order);
+    hipLaunchKernelGGL(count_kernel<View>, grid, block, 0, stream, view, d_bases, d_read_off, n_reads, d_mlen, d_occ, d_sp,
+                       d_order);
+}
+
+// Count queries over whatever layout the index holds (exactly one of its tables is live).
+inline void launch_count(const Index &ix, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads,
+                         uint32_t *d_mlen, uint64_t *d_occ, uint64_t *d_sp, const uint32_t *d_order, hipStream_t stream) {
+    if (n_reads == 0) return;
+    if (ix.line_rows())
+        launch_count_view(CountFatView{ix.table_fat()}, d_bases, d_read_off, n_reads, d_mlen, d_occ, d_sp, d_order, stream);
+    else if (ix.layout() == 3)
+        launch_count_view(CountSKView<3>{ix.table_k()}, d_bases, d_read_off, n_reads, d_mlen, d_occ, d_sp, d_order, stream);
+    else if (ix.layout() == 2)
+        launch_count_view(CountSKView<2>{ix.table_k()}, d_bases, d_read_off, n_reads, d_mlen, d_occ, d_sp, d_order, stream);
     else
-        hipLaunchKernelGGL(count_kernel<CountOneStepView>, grid, block, 0, stream, CountOneStepView{T1}, d_bases, d_read_off,
-                           n_reads, d_mlen, d_occ, d_sp, d_order);
+        launch_count_view(CountOneStepView{ix.table()}, d_bases, d_read_off, n_reads, d_mlen, d_occ, d_sp, d_order, stream);
 }
 
 }  // namespace colbwt

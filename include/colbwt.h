@@ -174,10 +174,10 @@ int colbwt_query_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_
  * n_reads entries, nullable) lists the read indices by decreasing length, so the
  * 64 lanes of a wave walk reads of similar length.  Results are identical with
  * or without it (each read's values only depend on that read); the host entry
- * points build the order themselves when a batch is ragged.  d_order is
- * ADVISORY: the K-step and one-step layouts assign lanes by it, the line-row
- * layout (COLBWT_LAYOUT_LINE_ROWS, the default) ignores it -- its persistent
- * lanes claim chunks of consecutive reads and balance ragged batches themselves. */
+ * points build the order themselves when a batch is ragged and the layout uses
+ * it.  d_order is ADVISORY: the one- and two-step layouts assign lanes by it,
+ * the three-step and line-row layouts ignore it -- their persistent lanes claim
+ * chunks of consecutive reads and balance ragged batches themselves. */
 int colbwt_query_device_ordered(colbwt_index *idx, const uint8_t *d_bases, const uint64_t *d_read_off,
                                 uint64_t n_reads, uint64_t n_bases, void *d_pml, int pml_bytes,
                                 uint8_t *d_cid, const uint32_t *d_order, void *hip_stream,

@@ -116,7 +116,61 @@ def main():
     ragged = helpers.reads_from_text(text, 200, (1, 400), 0.0, seed=10)
     check(img, ragged, "ragged batch", layouts=(1, 2))
     check_file(img, ragged[:50] + [np.zeros(0, np.uint8)])
+    check_replicas(img, ragged + [np.zeros(0, np.uint8)] * 2)
+    check_device(img, ragged[:120] + [np.zeros(0, np.uint8)] * 2)
     print("COUNT-EMU-OK")
+
+
+def aligned(n, dt, pad=0):
+    """A zeroed array of n items (+ pad spare bytes) that starts on a 64-byte boundary."""
+    size = n * np.dtype(dt).itemsize
+    raw = np.zeros(size + pad + 64, np.uint8)
+    o = (-raw.ctypes.data) % 64
+    return raw[o:o + size].view(dt)
+
+
+def check_replicas(image, reads):
+    """Two replicas (one shard each) == one replica, with sp; their stats add up."""
+    image = bytes(image)
+    bases, off = helpers.concat_reads(reads)
+    one = pkg.ColPml.from_bytes(image, layout=2)
+    two = pkg.ColPml.from_bytes(image, layout=2, devices=[0, 0])
+    assert two.info().n_devices == 2
+    m1, o1, s1, st1 = one.count_batch(bases, off, want_sp=True)
+    m2, o2, s2, st2 = two.count_batch(bases, off, want_sp=True)
+    assert np.array_equal(m1, m2) and np.array_equal(o1, o2) and np.array_equal(s1, s2)
+    for st in (st1, st2):
+        assert st.n_reads == len(reads) and st.n_bases == int(off[-1]) and st.algorithmic_bytes == 0, st.as_dict()
+    one.close(), two.close()
+    print(f"ok two replicas == one: {len(reads)} reads, {int(off[-1])} bases")
+
+
+def check_device(image, reads):
+    """colbwt_count_device with and without d_order (and d_sp) == colbwt_count_batch, layouts 1, 2, 3, 5."""
+    image = bytes(image)
+    bases, off = helpers.concat_reads(reads)
+    nr, nb = len(reads), int(off[-1])
+    d_bases = aligned(nb, np.uint8, pad=64)
+    d_bases[:nb] = bases
+    d_off = aligned(nr + 1, np.uint64)
+    d_off[:] = off
+    d_order = aligned(nr, np.uint32)
+    d_order[:] = np.argsort(-np.diff(off.astype(np.int64)), kind="stable")
+    for layout in (1, 2, 3, 5):
+        tbl = pkg.ColPml.from_bytes(image, layout=layout)
+        mlen, occ, sp, _ = tbl.count_batch(bases, off, want_sp=True)
+        for order in (None, d_order.ctypes.data):
+            d_mlen, d_occ, d_sp = aligned(nr, np.uint32), aligned(nr, np.uint64), aligned(nr, np.uint64)
+            st = tbl.count_device(d_bases.ctypes.data, d_off.ctypes.data, nr, nb, d_mlen.ctypes.data, d_occ.ctypes.data,
+                                  d_sp.ctypes.data, order, timed=True)
+            assert st.n_reads == nr and st.n_bases == nb and st.algorithmic_bytes == 0
+            assert np.array_equal(d_mlen, mlen) and np.array_equal(d_occ, occ) and np.array_equal(d_sp, sp), (layout, order)
+            d_mlen[:], d_occ[:] = 0, 0
+            tbl.count_device(d_bases.ctypes.data, d_off.ctypes.data, nr, nb, d_mlen.ctypes.data, d_occ.ctypes.data,
+                             None, order)
+            assert np.array_equal(d_mlen, mlen) and np.array_equal(d_occ, occ), (layout, order, "no sp")
+        tbl.close()
+    print(f"ok count_device == count_batch: {nr} reads, layouts 1, 2, 3, 5, with / without order and sp")
 
 
 if __name__ == "__main__":

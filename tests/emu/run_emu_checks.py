@@ -6,6 +6,7 @@ out-of-bounds access of the kernels / host logic is fatal.
 
 This is a test instrument: the shipped libcolbwt.so has no host path.
 """
+import ctypes
 import os
 import sys
 import tempfile
@@ -125,10 +126,6 @@ def main():
     print("ok binary containers, FASTA -> FASTQ hand-over, two replicas")
 
     # 1c. gather codec (multi-GPU exchange step): PML values <-> one bit per base
-    def aligned(n, dt):
-        raw = np.zeros(n * np.dtype(dt).itemsize + 64, np.uint8)
-        o = (-raw.ctypes.data) % 64
-        return raw[o:o + n * np.dtype(dt).itemsize].view(dt)
     creads = reads[:300] + [np.zeros(0, np.uint8)] * 3 + rand_reads(rng, 40, 1, 5)
     cb, coff = helpers.concat_reads(creads)
     epml, _ = oracle.OracleIndex(bytes(img)).query_batch(cb, coff)
@@ -325,7 +322,153 @@ def main():
         assert e.code == -6, e
     del os.environ["COLBWT_HBM_BUDGET_MB"]
     print(f"ok HBM budget fallback (index bytes by layout: {full})")
+
+    # 10. entry-point contracts: bad arguments (code, message, which check comes first) and the
+    #     device entry points == the host ones, with and without a lane order
+    check_bad_arguments(pkg.synth_index(300, mean_len=5, seed=41))
+    img = pkg.synth_index(1500, mean_len=6, split_permille=60, seed=42)
+    ragged = helpers.backward_walk_reads(img, 70, 150, 0.02, seed=43) + rand_reads(rng, 60, 0, 12)
+    ragged += [np.zeros(0, np.uint8)] * 3
+    check_device_equals_host(img, ragged)
     print("EMU-ALL-OK")
+
+
+def aligned(n, dt, shift=0):
+    """A zeroed array of n items whose data starts `shift` bytes past a 64-byte boundary."""
+    size = n * np.dtype(dt).itemsize
+    raw = np.zeros(size + 128, np.uint8)
+    o = (-raw.ctypes.data) % 64 + shift
+    return raw[o:o + size].view(dt)
+
+
+def call(fn, *args):
+    """(return code, colbwt_last_error() when the call failed)."""
+    rc = fn(*args)
+    return rc, pkg.lib().colbwt_last_error().decode() if rc else ""
+
+
+def check_bad_arguments(img):
+    """Return code and message of every bad argument of the batch entry points, in check order."""
+    L = pkg.lib()
+    tbl = pkg.ColPml.from_bytes(img, layout=2)
+    h = tbl._h
+    ARG = -1
+    off = np.array([0, 5, 9], np.uint64)
+    bad0 = np.array([1, 5, 9], np.uint64)
+    desc = np.array([0, 5, 4], np.uint64)
+    empty = np.zeros(4, np.uint64)                               # three empty reads
+    wide = np.array([0, 66000], np.uint64)
+    b = aligned(9 + 64, np.uint8)
+    p16, p32, c8 = aligned(16, np.uint16), aligned(16, np.uint32), aligned(16, np.uint8)
+    st = pkg.Stats()
+    for fn, pml, name in ((L.colbwt_query_batch, p16, "u16"), (L.colbwt_query_batch_u32, p32, "u32")):
+        P, B, C8 = pml.ctypes.data, b.ctypes.data, c8.ctypes.data
+        cases = [
+            ((None, B, off.ctypes.data, 2, P, C8, None), (ARG, "null index")),
+            ((h, None, None, 0, None, None, None), (0, "")),
+            ((h, B, None, 2, P, C8, None), (ARG, "null read_off")),
+            ((h, B, bad0.ctypes.data, 2, P, C8, None), (ARG, "read_off[0] must be 0")),
+            ((h, B, desc.ctypes.data, 2, P, C8, None), (ARG, "read_off not non-decreasing")),
+            ((h, None, empty.ctypes.data, 3, None, None, None), (0, "")),        # all reads empty: no pointer needed
+            ((h, None, off.ctypes.data, 2, P, C8, None), (ARG, "null bases/pml/cid")),
+            ((h, B, off.ctypes.data, 2, None, C8, None), (ARG, "null bases/pml/cid")),
+            ((h, B, off.ctypes.data, 2, P, None, None), (ARG, "null bases/pml/cid")),
+            # the length check comes before the pointer checks
+            ((h, None, wide.ctypes.data, 1, None, None, None),
+             (ARG, "read longer than 65535 bases: use colbwt_query_batch_u32") if name == "u16" else (ARG, "null bases/pml/cid")),
+        ]
+        for args, want in cases:
+            assert call(fn, *args) == want, (name, args, want, call(fn, *args))
+        st.n_reads = 99
+        assert fn(h, None, empty.ctypes.data, 3, None, None, ctypes.byref(st)) == 0 and st.n_reads == 3 and st.n_bases == 0
+        st.n_reads = 99
+        assert fn(h, None, None, 0, None, None, ctypes.byref(st)) == 0 and st.n_reads == 0
+
+    ml, oc, sp = aligned(4, np.uint32), aligned(4, np.uint64), aligned(4, np.uint64)
+    M, O, S, B = ml.ctypes.data, oc.ctypes.data, sp.ctypes.data, b.ctypes.data
+    fn = L.colbwt_count_batch
+    cases = [
+        ((None, B, off.ctypes.data, 2, M, O, S, None), (ARG, "null index")),
+        ((h, None, None, 0, None, None, None, None), (0, "")),
+        ((h, B, None, 2, M, O, S, None), (ARG, "null read_off")),
+        ((h, B, bad0.ctypes.data, 2, M, O, S, None), (ARG, "read_off[0] must be 0")),
+        ((h, B, desc.ctypes.data, 2, M, O, S, None), (ARG, "read_off not non-decreasing")),
+        ((h, None, off.ctypes.data, 2, M, O, S, None), (ARG, "null bases/mlen/occ")),
+        ((h, B, off.ctypes.data, 2, None, O, S, None), (ARG, "null bases/mlen/occ")),
+        ((h, B, off.ctypes.data, 2, M, None, S, None), (ARG, "null bases/mlen/occ")),
+        ((h, None, empty.ctypes.data, 3, None, O, None, None), (ARG, "null bases/mlen/occ")),   # outputs even for empty reads
+        ((h, B, off.ctypes.data, 2, M, O, None, None), (0, "")),            # sp is optional
+    ]
+    for args, want in cases:
+        assert call(fn, *args) == want, ("count", args, want, call(fn, *args))
+    ml[:], oc[:], sp[:] = 7, 7, 7
+    st.n_reads = 99
+    assert fn(h, None, empty.ctypes.data, 3, M, O, S, ctypes.byref(st)) == 0      # no bases: still one result per read
+    assert ml[:3].tolist() == [0, 0, 0] and oc[:3].tolist() == [0, 0, 0] and sp[:3].tolist() == [0, 0, 0] and ml[3] == 7
+    assert st.n_reads == 3 and st.n_bases == 0 and st.algorithmic_bytes == 0
+
+    # device entry points: pointers are only checked after pml_bytes (PML) and n_reads == 0
+    d_off = aligned(3, np.uint64)
+    d_off[:] = off
+    D, F = b.ctypes.data, d_off.ctypes.data
+    dp, dc = aligned(16, np.uint16).ctypes.data, c8.ctypes.data
+    msg_al = "d_bases/d_cid must be 16-byte aligned and d_pml 32-byte aligned"
+    for fn, extra in ((L.colbwt_query_device, ()), (L.colbwt_query_device_ordered, (None,))):
+        def q(h_, db, dof, n, dpml, pb, dcid):
+            return call(fn, h_, db, dof, n, 9, dpml, pb, dcid, *extra, None, None)
+        assert q(None, D, F, 2, dp, 2, dc) == (ARG, "null index")
+        assert q(h, None, None, 0, None, 3, None) == (ARG, "pml_bytes must be 2 or 4")
+        assert q(h, None, None, 0, None, 2, None) == (0, "")
+        for k in range(4):
+            args = [D, F, dp, dc]
+            args[k] = None
+            assert q(h, args[0], args[1], 2, args[2], 2, args[3]) == (ARG, "null device pointer"), k
+        assert q(h, D + 8, F, 2, dp, 2, dc) == (ARG, msg_al)
+        assert q(h, D, F, 2, dp + 16, 4, dc) == (ARG, msg_al)
+        assert q(h, D, F, 2, dp, 2, dc + 8) == (ARG, msg_al)
+    msg_al = "d_bases must be 16-byte aligned, d_mlen 4-byte and d_occ/d_sp 8-byte aligned"
+
+    def qc(h_, db, dof, n, dm, do, ds):
+        return call(L.colbwt_count_device, h_, db, dof, n, 9, dm, do, ds, None, None, None)
+    assert qc(None, D, F, 2, M, O, S) == (ARG, "null index")
+    assert qc(h, None, None, 0, None, None, None) == (0, "")
+    for k in range(4):
+        args = [D, F, M, O]
+        args[k] = None
+        assert qc(h, args[0], args[1], 2, args[2], args[3], S) == (ARG, "null device pointer"), k
+    for args in ((D + 8, F, 2, M, O, S), (D, F, 2, M + 2, O, S), (D, F, 2, M, O + 4, S), (D, F, 2, M, O, S + 4)):
+        assert qc(h, *args) == (ARG, msg_al), args
+    tbl.close()
+    print("ok bad arguments of the batch and device entry points")
+
+
+def length_order(off):
+    """Read indices by decreasing length (any order of equal lengths gives the same results)."""
+    return np.argsort(-np.diff(off.astype(np.int64)), kind="stable").astype(np.uint32)
+
+
+def check_device_equals_host(img, reads):
+    """colbwt_query_device[_ordered] with and without a d_order == colbwt_query_batch, layouts 1, 2, 3, 5."""
+    bases, off = helpers.concat_reads(reads)
+    nr, nb = len(reads), int(off[-1])
+    d_bases = aligned(nb + 64, np.uint8)
+    d_bases[:nb] = bases
+    d_off = aligned(nr + 1, np.uint64)
+    d_off[:] = off
+    d_order = aligned(nr, np.uint32)
+    d_order[:] = length_order(off)
+    for layout in (1, 2, 3, MIS_LINES):
+        tbl = pkg.ColPml.from_bytes(img, layout=layout)
+        pml, cid, st = tbl.query_batch(bases, off)
+        assert st.n_reads == nr and st.n_bases == nb and st.algorithmic_bytes == 27 * nb
+        for order in (None, d_order.ctypes.data):
+            d_pml, d_cid = aligned(nb + 16, np.uint16), aligned(nb + 16, np.uint8)
+            st = tbl.query_device(d_bases.ctypes.data, d_off.ctypes.data, nr, nb, d_pml.ctypes.data, d_cid.ctypes.data,
+                                  timed=True, d_order=order)
+            assert st.n_reads == nr and st.n_bases == nb and st.algorithmic_bytes == 27 * nb
+            assert np.array_equal(d_pml[:nb], pml) and np.array_equal(d_cid[:nb], cid), (layout, order is None)
+        tbl.close()
+    print(f"ok device entry point == host entry point: {nr} reads, {nb} bases, layouts 1, 2, 3, 5, with / without order")
 
 
 if __name__ == "__main__":
