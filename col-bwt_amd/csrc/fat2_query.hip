@@ -20,10 +20,6 @@
 // line fill per two bases instead of one per base.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
 
 #include "device_layout.h"
 #include "fat_cursor.h"
@@ -352,50 +348,14 @@ void fat2_query_kernel(FatTable T, const uint8_t *__restrict__ bases, const uint
 #endif
 }
 
-// Blocks that are resident at once on the device (LDS-bound: 3 per CU): the persistent grid.
-template <int K, typename PmlT, bool kDeep>
-uint32_t resident_blocks2() {
-    static uint32_t cached[16] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    if (cached[dev] == 0) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fat2_query_kernel<K, PmlT, kDeep>, kQueryBlock, 0) != hipSuccess || per_cu < 1)
-            per_cu = 1;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
-        (void)hipGetLastError();
-        cached[dev] = (uint32_t)per_cu * (uint32_t)cus;
-    }
-    return cached[dev];
-}
-
-template <int K, typename PmlT, bool kDeep>
-void launch_typed2(const FatTable &T, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads, uint64_t n_bases,
-                   PmlT *d_pml, uint8_t *d_cid, hipStream_t stream) {
-    const uint64_t want_blocks = (n_reads + kQueryBlock - 1) / kQueryBlock;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(want_blocks, resident_blocks2<K, PmlT, kDeep>());
-    // chunk sizes as in fat_query.hip (launch_typed)
-    const uint64_t lanes = (uint64_t)blocks * kQueryBlock;
-    const uint64_t avg_len = std::max<uint64_t>(n_bases / std::max<uint64_t>(n_reads, 1), 1);
-    uint32_t big = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(n_bases / lanes / 6 / avg_len, 1), 8);
-    uint32_t tail_permille = 100;
-    if (const char *e = getenv("COLBWT_LINE_ROWS_CHUNK")) {   // experiments: "<big>[,<tail permille>]"
-        const int v = atoi(e);
-        if (v >= 1 && v <= 1024) big = (uint32_t)v;
-        if (const char *c = strchr(e, ',')) tail_permille = (uint32_t)std::min(1000, std::max(0, atoi(c + 1)));
-    }
-    hipLaunchKernelGGL((fat2_query_kernel<K, PmlT, kDeep>), dim3(blocks), dim3(kQueryBlock), 0, stream, T, d_bases, d_read_off, n_reads,
-                       big, tail_permille, d_pml, d_cid);
-}
-
 template <int K>
 void launch_steps2(const FatTable &T, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads, uint64_t n_bases,
                    void *d_pml, int pml_bytes, uint8_t *d_cid, hipStream_t stream) {
     const bool deep = T.entry_shift == 7;
-    if (pml_bytes == 2 && deep) launch_typed2<K, uint16_t, true>(T, d_bases, d_read_off, n_reads, n_bases, (uint16_t *)d_pml, d_cid, stream);
-    else if (pml_bytes == 2) launch_typed2<K, uint16_t, false>(T, d_bases, d_read_off, n_reads, n_bases, (uint16_t *)d_pml, d_cid, stream);
-    else if (deep) launch_typed2<K, uint32_t, true>(T, d_bases, d_read_off, n_reads, n_bases, (uint32_t *)d_pml, d_cid, stream);
-    else launch_typed2<K, uint32_t, false>(T, d_bases, d_read_off, n_reads, n_bases, (uint32_t *)d_pml, d_cid, stream);
+    if (pml_bytes == 2 && deep) launch_persistent<fat2_query_kernel<K, uint16_t, true>>(T, d_bases, d_read_off, n_reads, n_bases, (uint16_t *)d_pml, d_cid, stream);
+    else if (pml_bytes == 2) launch_persistent<fat2_query_kernel<K, uint16_t, false>>(T, d_bases, d_read_off, n_reads, n_bases, (uint16_t *)d_pml, d_cid, stream);
+    else if (deep) launch_persistent<fat2_query_kernel<K, uint32_t, true>>(T, d_bases, d_read_off, n_reads, n_bases, (uint32_t *)d_pml, d_cid, stream);
+    else launch_persistent<fat2_query_kernel<K, uint32_t, false>>(T, d_bases, d_read_off, n_reads, n_bases, (uint32_t *)d_pml, d_cid, stream);
 }
 
 }  // namespace

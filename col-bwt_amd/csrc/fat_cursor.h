@@ -1,10 +1,16 @@
-// fat_cursor.h -- what the two line-row query kernels (fat_query.hip: in-row mismatch slots,
-// fat2_query.hip: mismatch lines) share: arrival codes, the run-time threshold_step for characters
-// without a slot, and the persistent lanes' chunk plan / read cursor.  Everything lives in an
-// unnamed namespace: each translation unit gets its own copy.
+// fat_cursor.h -- what the three persistent-lane query kernels (fat_query.hip: line rows with in-row
+// mismatch slots, fat2_query.hip: line rows with mismatch lines, sk3_query.hip: three-step rows)
+// share: arrival codes, the run-time threshold_step of the line rows for characters without a slot,
+// the persistent lanes' chunk plan / read cursor, and the host launch of their grid
+// (launch_persistent).  Everything lives in an unnamed namespace: each translation unit gets its
+// own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
 
 #include "device_layout.h"
 #include "fat_layout.h"
@@ -139,6 +145,41 @@ struct ReadCursor {
         return true;
     }
 };
+
+// Launch of a persistent query kernel (fat_query_kernel, fat2_query_kernel, sk3_query_kernel: the
+// arguments after the table are the same for all three).  The grid is the workgroups resident at
+// once on the device (LDS-bound: 3 per CU), cached per device and kernel.  Reads per bulk chunk: a
+// chunk ends with a ragged flush of the collector, so it should hold a few reads -- but no more than
+// a sixth of a lane's share of the BASES, or a few lanes end up with most of a workgroup's work (1 M
+// reads of 10 kbp are five reads per lane: chunks of eight took 1.6 times as long as single reads).
+// The last tenth of a workgroup's share (at least two reads per lane) goes out read by read.
+template <auto kKernel, typename Table, typename PmlT>
+void launch_persistent(const Table &T, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads, uint64_t n_bases,
+                       PmlT *d_pml, uint8_t *d_cid, hipStream_t stream) {
+    static uint32_t resident[16] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
+    if (resident[dev] == 0) {
+        int per_cu = 0, cus = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kKernel, kQueryBlock, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
+        (void)hipGetLastError();
+        resident[dev] = (uint32_t)per_cu * (uint32_t)cus;
+    }
+    const uint64_t want_blocks = (n_reads + kQueryBlock - 1) / kQueryBlock;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>(want_blocks, resident[dev]);
+    const uint64_t lanes = (uint64_t)blocks * kQueryBlock;
+    const uint64_t avg_len = std::max<uint64_t>(n_bases / std::max<uint64_t>(n_reads, 1), 1);
+    uint32_t big = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(n_bases / lanes / 6 / avg_len, 1), 8);
+    uint32_t tail_permille = 100;
+    if (const char *e = getenv("COLBWT_LINE_ROWS_CHUNK")) {   // experiments: "<big>[,<tail permille>]"
+        const int v = atoi(e);
+        if (v >= 1 && v <= 1024) big = (uint32_t)v;
+        if (const char *c = strchr(e, ',')) tail_permille = (uint32_t)std::min(1000, std::max(0, atoi(c + 1)));
+    }
+    hipLaunchKernelGGL(kKernel, dim3(blocks), dim3(kQueryBlock), 0, stream, T, d_bases, d_read_off, n_reads, big, tail_permille, d_pml,
+                       d_cid);
+}
 
 }  // namespace
 

@@ -22,11 +22,6 @@
 // fetches its share of the other lanes' rows.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
-
-#include <string.h>
-
-#include <algorithm>
 
 #include "device_layout.h"
 #include "fat_cursor.h"
@@ -280,51 +275,11 @@ void fat_query_kernel(FatTable T, const uint8_t *__restrict__ bases, const uint6
 #endif
 }
 
-// Blocks that are resident at once on the device (LDS-bound: 3 per CU): the persistent grid.
-template <int K, typename PmlT>
-uint32_t resident_blocks() {
-    static uint32_t cached[16] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    if (cached[dev] == 0) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fat_query_kernel<K, PmlT>, kQueryBlock, 0) != hipSuccess || per_cu < 1)
-            per_cu = 1;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
-        (void)hipGetLastError();
-        cached[dev] = (uint32_t)per_cu * (uint32_t)cus;
-    }
-    return cached[dev];
-}
-
-template <int K, typename PmlT>
-void launch_typed(const FatTable &T, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads, uint64_t n_bases,
-                  PmlT *d_pml, uint8_t *d_cid, hipStream_t stream) {
-    const uint64_t want_blocks = (n_reads + kQueryBlock - 1) / kQueryBlock;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(want_blocks, resident_blocks<K, PmlT>());
-    // Reads per bulk chunk: a chunk ends with a ragged flush of the collector, so it should hold a
-    // few reads -- but no more than a sixth of a lane's share of the BASES, or a few lanes end up
-    // with most of a workgroup's work (1 M reads of 10 kbp are five reads per lane: chunks of eight
-    // took 1.6 times as long as single reads).  The last tenth of a workgroup's share (at least two
-    // reads per lane) goes out read by read.
-    const uint64_t lanes = (uint64_t)blocks * kQueryBlock;
-    const uint64_t avg_len = std::max<uint64_t>(n_bases / std::max<uint64_t>(n_reads, 1), 1);
-    uint32_t big = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(n_bases / lanes / 6 / avg_len, 1), 8);
-    uint32_t tail_permille = 100;
-    if (const char *e = getenv("COLBWT_LINE_ROWS_CHUNK")) {   // experiments: "<big>[,<tail permille>]"
-        const int v = atoi(e);
-        if (v >= 1 && v <= 1024) big = (uint32_t)v;
-        if (const char *c = strchr(e, ',')) tail_permille = (uint32_t)std::min(1000, std::max(0, atoi(c + 1)));
-    }
-    hipLaunchKernelGGL((fat_query_kernel<K, PmlT>), dim3(blocks), dim3(kQueryBlock), 0, stream, T, d_bases, d_read_off, n_reads,
-                       big, tail_permille, d_pml, d_cid);
-}
-
 template <int K>
 void launch_steps(const FatTable &T, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads, uint64_t n_bases,
                   void *d_pml, int pml_bytes, uint8_t *d_cid, hipStream_t stream) {
-    if (pml_bytes == 2) launch_typed<K, uint16_t>(T, d_bases, d_read_off, n_reads, n_bases, (uint16_t *)d_pml, d_cid, stream);
-    else launch_typed<K, uint32_t>(T, d_bases, d_read_off, n_reads, n_bases, (uint32_t *)d_pml, d_cid, stream);
+    if (pml_bytes == 2) launch_persistent<fat_query_kernel<K, uint16_t>>(T, d_bases, d_read_off, n_reads, n_bases, (uint16_t *)d_pml, d_cid, stream);
+    else launch_persistent<fat_query_kernel<K, uint32_t>>(T, d_bases, d_read_off, n_reads, n_bases, (uint32_t *)d_pml, d_cid, stream);
 }
 
 }  // namespace

@@ -16,10 +16,6 @@
 //     stored 32-byte PML and 16-byte col-id pieces, the expensive kind (tools/scatter_bench).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <algorithm>
 
 #include "device_layout.h"
 #include "fat_cursor.h"
@@ -260,42 +256,14 @@ void sk3_query_kernel(SKTable T, const uint8_t *__restrict__ bases, const uint64
     }
 }
 
-template <typename PmlT>
-uint32_t resident_blocks3() {
-    static uint32_t cached[16] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) dev = 0;
-    if (cached[dev] == 0) {
-        int per_cu = 0, cus = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sk3_query_kernel<PmlT>, kQueryBlock, 0) != hipSuccess || per_cu < 1)
-            per_cu = 1;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) cus = 1;
-        (void)hipGetLastError();
-        cached[dev] = (uint32_t)per_cu * (uint32_t)cus;
-    }
-    return cached[dev];
-}
-
-template <typename PmlT>
-void launch_typed3(const SKTable &T, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads, uint64_t n_bases,
-                   PmlT *d_pml, uint8_t *d_cid, hipStream_t stream) {
-    const uint64_t want_blocks = (n_reads + kQueryBlock - 1) / kQueryBlock;
-    const uint32_t blocks = (uint32_t)std::min<uint64_t>(want_blocks, resident_blocks3<PmlT>());
-    const uint64_t lanes = (uint64_t)blocks * kQueryBlock;     // chunk sizes as in fat_query.hip (launch_typed)
-    const uint64_t avg_len = std::max<uint64_t>(n_bases / std::max<uint64_t>(n_reads, 1), 1);
-    const uint32_t big = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(n_bases / lanes / 6 / avg_len, 1), 8);
-    hipLaunchKernelGGL((sk3_query_kernel<PmlT>), dim3(blocks), dim3(kQueryBlock), 0, stream, T, d_bases, d_read_off, n_reads, big,
-                       100u, d_pml, d_cid);
-}
-
 }  // namespace
 
 // The three-step query with persistent lanes and pair-fetched rows.  n_bases = read_off[n_reads] - read_off[0].
 void launch_sk3_query(const SKTable &T, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads, uint64_t n_bases,
                       void *d_pml, int pml_bytes, uint8_t *d_cid, hipStream_t stream) {
     if (n_reads == 0) return;
-    if (pml_bytes == 2) launch_typed3<uint16_t>(T, d_bases, d_read_off, n_reads, n_bases, (uint16_t *)d_pml, d_cid, stream);
-    else launch_typed3<uint32_t>(T, d_bases, d_read_off, n_reads, n_bases, (uint32_t *)d_pml, d_cid, stream);
+    if (pml_bytes == 2) launch_persistent<sk3_query_kernel<uint16_t>>(T, d_bases, d_read_off, n_reads, n_bases, (uint16_t *)d_pml, d_cid, stream);
+    else launch_persistent<sk3_query_kernel<uint32_t>>(T, d_bases, d_read_off, n_reads, n_bases, (uint32_t *)d_pml, d_cid, stream);
 }
 
 }  // namespace colbwt
