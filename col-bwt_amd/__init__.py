@@ -31,7 +31,12 @@ EXPORTS = (
     "colbwt_col_split", "colbwt_col_split_arrays", "colbwt_col_split_error",
     "colbwt_rlbwt_build_text", "colbwt_rlbwt_build_files", "colbwt_rlbwt_get", "colbwt_rlbwt_free", "colbwt_rlbwt_error",
     "colbwt_count_batch", "colbwt_count_device", "colbwt_count_file",
+    "colbwt_index_attach_locate", "colbwt_index_attach_locate_memory", "colbwt_locate_docs", "colbwt_locate_batch",
+    "colbwt_locate_device", "colbwt_locate_file",
+    "colbwt_rlbwt_build_text_locate", "colbwt_rlbwt_build_files_locate", "colbwt_rlbwt_write_locate",
 )
+
+LOCATE_NONE = (1 << 64) - 1     # include/colbwt.h COLBWT_LOCATE_NONE: a position slot past the read's min(occ, max_occ)
 
 
 class ColbwtError(RuntimeError):
@@ -112,6 +117,16 @@ def lib():
     L.colbwt_count_batch.argtypes = [vp, vp, vp, u64, vp, vp, vp, C.POINTER(Stats)]
     L.colbwt_count_device.argtypes = [vp, vp, vp, u64, u64, vp, vp, vp, vp, vp, C.POINTER(Stats)]
     L.colbwt_count_file.argtypes = [vp, C.c_char_p, C.c_char_p, u64, C.POINTER(Stats)]
+    u32 = C.c_uint32
+    L.colbwt_index_attach_locate.argtypes = [vp, C.c_char_p]
+    L.colbwt_index_attach_locate_memory.argtypes = [vp, vp, u64]
+    L.colbwt_locate_docs.argtypes = [vp, vp, u32, C.POINTER(u32)]
+    L.colbwt_locate_batch.argtypes = [vp, vp, vp, u64, u32, vp, vp, vp, C.POINTER(Stats)]
+    L.colbwt_locate_device.argtypes = [vp, vp, vp, u64, u64, u32, vp, vp, vp, vp, vp, C.POINTER(Stats)]
+    L.colbwt_locate_file.argtypes = [vp, C.c_char_p, C.c_char_p, u32, u64, C.POINTER(Stats)]
+    L.colbwt_rlbwt_build_text_locate.argtypes = [vp, u64, vp, u32, u64, C.c_int, C.POINTER(vp)]
+    L.colbwt_rlbwt_build_files_locate.argtypes = [C.POINTER(C.c_char_p), u32, C.c_int, u64, C.c_int, C.c_char_p, C.POINTER(vp)]
+    L.colbwt_rlbwt_write_locate.argtypes = [vp, C.c_char_p]
     _lib = L
     return L
 
@@ -255,6 +270,61 @@ class ColPml:
                                        batch_bases, C.byref(st)))
         return st
 
+    # -- locate (include/colbwt.h colbwt_locate_*) -------------------------------------------------
+    def attach_locate(self, prefix_or_file=None, data=None):
+        """Loads the locate samples onto every replica: <prefix>.col_loc (or the path itself), or a
+        .col_loc image in memory (`data`, bytes-like)."""
+        if data is not None:
+            arr = np.ascontiguousarray(np.frombuffer(bytes(data), dtype=np.uint8))
+            _check(lib().colbwt_index_attach_locate_memory(self._h, arr.ctypes.data, arr.size))
+        else:
+            _check(lib().colbwt_index_attach_locate(self._h, os.fsencode(prefix_or_file)))
+
+    def locate_docs(self):
+        """doc_start of the attached samples (uint64 array): first text position of every document."""
+        n = C.c_uint32(0)
+        L = lib()
+        L.colbwt_locate_docs(self._h, None, 0, C.byref(n))     # their number (the call itself fails for want of room)
+        out = np.zeros(n.value, np.uint64)
+        _check(L.colbwt_locate_docs(self._h, out.ctypes.data, n.value, C.byref(n)))
+        return out
+
+    def locate_batch(self, bases, read_off, max_occ=16):
+        """Many reads -> (mlen uint32, occ uint64, pos uint64 [n_reads, max_occ], Stats): pos[k, :min(occ, max_occ)]
+        are the text positions SA[ep], SA[ep-1], .. of read k's longest matching suffix, the rest LOCATE_NONE."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        n_reads = max(read_off.size - 1, 0)
+        mlen = np.zeros(n_reads, np.uint32)
+        occ = np.zeros(n_reads, np.uint64)
+        pos = np.zeros((n_reads, max(int(max_occ), 0)), np.uint64)
+        st = Stats()
+        _check(lib().colbwt_locate_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n_reads, int(max_occ),
+                                         mlen.ctypes.data, occ.ctypes.data, pos.ctypes.data, C.byref(st)))
+        return mlen, occ, pos, st
+
+    def locate(self, pattern, max_occ=16):
+        """One read -> (mlen, occ, [positions]) as ints (at most max_occ positions)."""
+        p = np.frombuffer(bytes(pattern), dtype=np.uint8)
+        mlen, occ, pos, _ = self.locate_batch(p, np.array([0, p.size], np.uint64), max_occ)
+        k = min(int(occ[0]), int(max_occ))
+        return int(mlen[0]), int(occ[0]), [int(x) for x in pos[0, :k]]
+
+    def locate_device(self, d_bases, d_read_off, n_reads, n_bases, max_occ, d_mlen, d_occ, d_pos, d_order=None, stream=0,
+                      timed=False):
+        """Device-resident locate entry point: raw device pointers (ints); d_pos holds n_reads * max_occ u64."""
+        st = Stats()
+        _check(lib().colbwt_locate_device(self._h, d_bases, d_read_off, n_reads, n_bases, int(max_occ), d_mlen, d_occ, d_pos,
+                                          d_order, stream, C.byref(st) if timed else None))
+        return st
+
+    def locate_file(self, pattern_path, out_path=None, max_occ=16, batch_bases=0):
+        """FASTA/FASTQ(.gz) -> text lines "name\tm\tmlen\tocc\tdoc:offset,.." (default <pattern>.locate)."""
+        st = Stats()
+        _check(lib().colbwt_locate_file(self._h, os.fsencode(pattern_path), os.fsencode(out_path) if out_path else None,
+                                        int(max_occ), batch_bases, C.byref(st)))
+        return st
+
     def cid_dictionary(self):
         """The distinct col ids the table's rows hold, ascending (uint8 array): the dictionary of the gather codec."""
         ids = np.zeros(256, np.uint8)
@@ -276,6 +346,15 @@ class ColPml:
             self.close()
         except Exception:
             pass
+
+
+def doc_offsets(positions, doc_start):
+    """Text positions -> (document number, offset inside the document) arrays (LOCATE_NONE entries are
+    left out by the caller; doc_start from ColPml.locate_docs)."""
+    positions = np.asarray(positions, np.uint64)
+    doc_start = np.asarray(doc_start, np.uint64)
+    doc = np.searchsorted(doc_start, positions, side="right").astype(np.int64) - 1
+    return doc, positions - doc_start[doc]
 
 
 def binary_to_text(bin_path, value_bytes, text_path):
@@ -414,32 +493,43 @@ def _rlbwt_result(L, handle):
     return out
 
 
-def rlbwt_from_text(text, doc_start, min_mum=20, device=0):
+def rlbwt_from_text(text, doc_start, min_mum=20, device=0, locate_path=None):
     """RLBWT, thresholds and multi-MUMs of a prepared text (separators 1, final 0) on the device:
-    -> dict(n, n_docs, rounds, heads, lens, thr, mum_len, mum_pos)."""
+    -> dict(n, n_docs, rounds, heads, lens, thr, mum_len, mum_pos).  locate_path: also gathers the
+    locate samples and writes them there as a .col_loc."""
     L = lib()
     L.colbwt_rlbwt_error.restype = C.c_char_p
     L.colbwt_rlbwt_build_text.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
     t = np.frombuffer(bytes(text), np.uint8)
     ds = np.ascontiguousarray(doc_start, np.uint64)
     h = C.c_void_p()
-    rc = L.colbwt_rlbwt_build_text(t.ctypes.data, t.size, ds.ctypes.data, ds.size, int(min_mum), int(device), C.byref(h))
+    fn = L.colbwt_rlbwt_build_text_locate if locate_path else L.colbwt_rlbwt_build_text
+    rc = fn(t.ctypes.data, t.size, ds.ctypes.data, ds.size, int(min_mum), int(device), C.byref(h))
+    if rc == 0 and locate_path:
+        rc = L.colbwt_rlbwt_write_locate(h, os.fsencode(locate_path))
+        if rc != 0:
+            msg = L.colbwt_rlbwt_error().decode()
+            L.colbwt_rlbwt_free.argtypes = [C.c_void_p]
+            L.colbwt_rlbwt_free(h)
+            raise ColbwtError(rc, msg)
     if rc != 0:
         raise ColbwtError(rc, L.colbwt_rlbwt_error().decode())
     return _rlbwt_result(L, h)
 
 
-def rlbwt_from_fastas(paths, out_prefix=None, min_mum=20, revcomp=False, device=0):
+def rlbwt_from_fastas(paths, out_prefix=None, min_mum=20, revcomp=False, device=0, locate=False):
     """`mumemto mum -K -R -T` of the reference's driver (col-bwt.py:121-145): one document per file;
-    writes <out_prefix>.bwt.heads / .bwt.len / .thr_pos / .col_mums when given; returns the arrays."""
+    writes <out_prefix>.bwt.heads / .bwt.len / .thr_pos / .col_mums (and with `locate` <out_prefix>.col_loc)
+    when given; returns the arrays."""
     L = lib()
     L.colbwt_rlbwt_error.restype = C.c_char_p
     L.colbwt_rlbwt_build_files.argtypes = [C.POINTER(C.c_char_p), C.c_uint32, C.c_int, C.c_uint64, C.c_int, C.c_char_p,
                                            C.POINTER(C.c_void_p)]
     arr = (C.c_char_p * len(paths))(*[os.fsencode(p) for p in paths])
     h = C.c_void_p()
-    rc = L.colbwt_rlbwt_build_files(arr, len(paths), int(bool(revcomp)), int(min_mum), int(device),
-                                    os.fsencode(out_prefix) if out_prefix else None, C.byref(h))
+    fn = L.colbwt_rlbwt_build_files_locate if locate else L.colbwt_rlbwt_build_files
+    rc = fn(arr, len(paths), int(bool(revcomp)), int(min_mum), int(device), os.fsencode(out_prefix) if out_prefix else None,
+            C.byref(h))
     if rc != 0:
         raise ColbwtError(rc, L.colbwt_rlbwt_error().decode())
     return _rlbwt_result(L, h)

@@ -26,6 +26,7 @@
 #include "fasta_parallel.h"
 #include "fastx_reader.h"
 #include "index.h"
+#include "locate_query.h"
 #include "query_kernels.h"
 #include "text_writer.h"
 
@@ -105,6 +106,24 @@ private:
 
 constexpr int kFileBatches = 3;   // batches of reads in flight in colbwt_query_file
 
+// The locate samples of one replica (colbwt_index_attach_locate): the toehold of every row of the
+// layout in HBM that ends a folded run, the phi samples and their bucket directory.
+struct LocateTables {
+    DevPtr toe_row, pair, dir;
+    uint32_t shift = 0;
+    uint64_t n_buckets = 0;
+    std::vector<uint64_t> doc_start;    // host copy: positions -> (document, offset) in colbwt_locate_file
+    bool ready() const { return toe_row.get() != nullptr; }
+    uint64_t bytes() const { return toe_row.bytes() + pair.bytes() + dir.bytes(); }
+    PhiTable phi() const { return PhiTable{pair.as<const uint2>(), dir.as<const uint32_t>(), shift, (uint32_t)(n_buckets - 1)}; }
+    void reset() {
+        toe_row.reset();
+        pair.reset();
+        dir.reset();
+        doc_start.clear();
+    }
+};
+
 struct colbwt_index {
     Index ix;
     // result arrays of colbwt_query_file's batches (one file query at a time uses them)
@@ -122,10 +141,12 @@ struct colbwt_index {
     std::mutex stage_mu;
     void *stage[2] = {nullptr, nullptr};
     size_t stage_bytes = 0;
+    LocateTables loc;
     ~colbwt_index() {
         for (colbwt_index *r : more) delete r;
         if (ix.device() >= 0) (void)hipSetDevice(ix.device());
         scratch.release();
+        loc.reset();
         for (void *p : stage)
             if (p) (void)hipHostFree(p);
     }
@@ -545,6 +566,142 @@ int count_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *rea
                          part);
 }
 
+// Largest max_occ: results are n_reads x max_occ u64 slots, in host memory and in HBM.
+constexpr uint32_t kLocateMaxOcc = 1u << 20;
+
+// Locate queries (locate_query.h) for a batch in host memory: mlen and occ per read, max_occ slots
+// of positions per read.  Every replica needs its samples attached.
+int locate_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t max_occ,
+                     uint32_t *mlen, uint64_t *occ, uint64_t *pos, colbwt_stats *stats) {
+    if (idx && (max_occ == 0 || max_occ > kLocateMaxOcc)) return fail(COLBWT_ERR_ARG, "max_occ must be 1 .. 2^20");
+    if (idx) {
+        if (!idx->loc.ready()) return fail(COLBWT_ERR_ARG, "no locate samples attached (colbwt_index_attach_locate)");
+        for (colbwt_index *r : idx->more)
+            if (!r->loc.ready()) return fail(COLBWT_ERR_ARG, "no locate samples attached (colbwt_index_attach_locate)");
+    }
+    auto bad_pointers = [&](uint64_t n_bases) -> const char * {
+        return (n_bases && !bases) || !mlen || !occ || !pos ? "null bases/mlen/occ/pos" : nullptr;
+    };
+    auto part = [&](colbwt_index *rep, uint64_t lo, uint64_t hi, uint64_t max_len, uint64_t min_len, colbwt_stats *st,
+                    std::string &msg) {
+        const uint64_t n = hi - lo, off0 = read_off[lo];
+        const uint64_t out_bytes[2] = {n * sizeof(uint32_t), (n + n * max_occ) * sizeof(uint64_t)};   // mlen; occ, then pos
+        auto launch = [&](const DeviceBatch &b) {
+            uint64_t *d_occ = (uint64_t *)b.out[1];
+            launch_locate(rep->ix, rep->loc.toe_row.as<uint32_t>(), rep->loc.phi(), b.bases, b.off, n, max_occ,
+                          (uint32_t *)b.out[0], d_occ, d_occ + n, b.order, b.stream);
+        };
+        auto fetch = [&](const DeviceBatch &b) {
+            const uint64_t *d_occ = (const uint64_t *)b.out[1];
+            TRY_HIP(hipMemcpyAsync(mlen + lo, b.out[0], n * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            TRY_HIP(hipMemcpyAsync(occ + lo, d_occ, n * sizeof(uint64_t), hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            TRY_HIP(hipMemcpyAsync(pos + lo * max_occ, d_occ + n, n * max_occ * sizeof(uint64_t), hipMemcpyDeviceToHost, b.stream),
+                    b.stream, msg);
+            return COLBWT_OK;
+        };
+        return replica_batch(rep, bases + off0, read_off + lo, off0, n, max_len, min_len, true, out_bytes, 0, st, msg, launch,
+                             fetch);
+    };
+    return sharded_batch(idx, read_off, n_reads, 0xFFFFFFFFull, "read longer than 2^32-1 bases", true, stats, bad_pointers,
+                         part);
+}
+
+// ---- .col_loc (include/colbwt.h): header, end_sa[r], phi pairs[s], doc_start[n_docs] ----
+constexpr uint64_t kLocHeader = 40;
+const char kLocMagic[8] = {'C', 'O', 'L', 'B', 'W', 'T', 'L', 'C'};
+
+struct LocFile {
+    uint64_t n = 0, r = 0, s = 0;
+    uint32_t n_docs = 0;
+    const uint32_t *end_sa = nullptr, *pair = nullptr, *doc_start = nullptr;
+};
+
+// Everything that can be checked without the device: header, length, value ranges, sorted phi positions.
+int parse_loc(const uint8_t *p, uint64_t len, const Index &ix, LocFile &f, std::string &msg) {
+    uint32_t version = 0;
+    if (len < kLocHeader || memcmp(p, kLocMagic, 8) != 0) { msg = "not a .col_loc file (magic)"; return COLBWT_ERR_FORMAT; }
+    memcpy(&version, p + 8, 4);
+    memcpy(&f.n_docs, p + 12, 4);
+    memcpy(&f.n, p + 16, 8);
+    memcpy(&f.r, p + 24, 8);
+    memcpy(&f.s, p + 32, 8);
+    if (version != 1) { msg = ".col_loc version " + std::to_string(version) + " (1 expected)"; return COLBWT_ERR_FORMAT; }
+    if (f.n != ix.n()) { msg = ".col_loc n = " + std::to_string(f.n) + ", the table's n = " + std::to_string(ix.n()); return COLBWT_ERR_FORMAT; }
+    if (f.r != ix.bwt_r()) { msg = ".col_loc r = " + std::to_string(f.r) + ", the table's bwt_r = " + std::to_string(ix.bwt_r()); return COLBWT_ERR_FORMAT; }
+    if (f.s == 0 || f.s > f.n || f.n_docs == 0 || f.n_docs > f.n) { msg = ".col_loc: bad sample or document count"; return COLBWT_ERR_FORMAT; }
+    if (len != kLocHeader + 4 * f.r + 8 * f.s + 4 * (uint64_t)f.n_docs) { msg = ".col_loc: file length does not match its header"; return COLBWT_ERR_FORMAT; }
+    if ((uintptr_t)p & 3) { msg = ".col_loc image must be 4-byte aligned"; return COLBWT_ERR_ARG; }
+    f.end_sa = (const uint32_t *)(p + kLocHeader);
+    f.pair = f.end_sa + f.r;
+    f.doc_start = f.pair + 2 * f.s;
+    for (uint64_t i = 0; i < f.r; ++i)
+        if (f.end_sa[i] >= f.n) { msg = ".col_loc: end_sa[" + std::to_string(i) + "] >= n"; return COLBWT_ERR_FORMAT; }
+    if (f.pair[0] != 0) { msg = ".col_loc: the first phi sample is not position 0"; return COLBWT_ERR_FORMAT; }
+    for (uint64_t i = 0; i < f.s; ++i) {
+        if (f.pair[2 * i] >= f.n || f.pair[2 * i + 1] >= f.n) { msg = ".col_loc: phi sample " + std::to_string(i) + " >= n"; return COLBWT_ERR_FORMAT; }
+        if (i && f.pair[2 * i] <= f.pair[2 * i - 2]) { msg = ".col_loc: phi positions do not ascend at sample " + std::to_string(i); return COLBWT_ERR_FORMAT; }
+    }
+    for (uint32_t d = 0; d < f.n_docs; ++d)
+        if (f.doc_start[d] >= f.n || (d ? f.doc_start[d] <= f.doc_start[d - 1] : f.doc_start[0] != 0)) {
+            msg = ".col_loc: document starts must ascend from 0";
+            return COLBWT_ERR_FORMAT;
+        }
+    return COLBWT_OK;
+}
+
+// The samples onto one replica: end_sa scattered to the layout's run-ending rows (whose number must be
+// r), the phi pairs and their directory.  On failure the replica keeps no locate tables.
+int attach_one(colbwt_index *rep, const LocFile &f, std::string &msg) {
+    rep->loc.reset();
+    int rc = select_device(rep->ix.device(), msg);
+    if (rc != COLBWT_OK) return rc;
+    LocateTables &L = rep->loc;
+    const uint64_t rows = rep->ix.table_rows();
+    // shift: buckets of 2^shift positions, 2^shift <= n / s < 2^(shift+1) -- about one sample per bucket
+    // and a directory of s .. 2s entries
+    uint32_t shift = 0;
+    while (shift < 31 && (f.s << (shift + 1)) <= f.n) ++shift;
+    const uint64_t n_buckets = ((f.n - 1) >> shift) + 1;
+    DevPtr flag, sel, count, tmp, end_sa;
+    size_t tmp_bytes = 0;
+    TRY_HIP(hipcub::DeviceSelect::Flagged(nullptr, tmp_bytes, hipcub::CountingInputIterator<uint32_t>(0), (uint8_t *)nullptr,
+                                          (uint32_t *)nullptr, (unsigned long long *)nullptr, (size_t)rows),
+            nullptr, msg);
+    TRY_HIP(flag.alloc(rows), nullptr, msg);
+    TRY_HIP(sel.alloc(4 * rows), nullptr, msg);
+    TRY_HIP(count.alloc(8), nullptr, msg);
+    TRY_HIP(tmp.alloc(tmp_bytes + 256), nullptr, msg);
+    TRY_HIP(end_sa.alloc(4 * f.r), nullptr, msg);
+    TRY_HIP(L.toe_row.alloc(4 * rows), nullptr, msg);
+    TRY_HIP(L.pair.alloc(8 * f.s), nullptr, msg);
+    TRY_HIP(L.dir.alloc(4 * (n_buckets + 1)), nullptr, msg);
+    TRY_HIP(hipMemcpy(end_sa.get(), f.end_sa, 4 * f.r, hipMemcpyHostToDevice), nullptr, msg);
+    TRY_HIP(hipMemcpy(L.pair.get(), f.pair, 8 * f.s, hipMemcpyHostToDevice), nullptr, msg);
+    TRY_HIP(hipMemset(L.toe_row.get(), 0, 4 * rows), nullptr, msg);
+    TRY_HIP(run_end_rows(rep->ix, flag.as<uint8_t>(), sel.as<uint32_t>(), count.as<unsigned long long>(), tmp.get(), tmp_bytes + 256,
+                         nullptr),
+            nullptr, msg);
+    unsigned long long ends = 0;
+    TRY_HIP(hipMemcpy(&ends, count.get(), 8, hipMemcpyDeviceToHost), nullptr, msg);
+    if (ends != f.r) {
+        L.reset();
+        msg = "the table has " + std::to_string(ends) + " rows that end a run, the .col_loc " + std::to_string(f.r) + " runs";
+        return COLBWT_ERR_FORMAT;
+    }
+    const uint32_t *p_sel = sel.as<uint32_t>(), *p_end = end_sa.as<uint32_t>();
+    uint32_t *p_toe = L.toe_row.as<uint32_t>(), *p_dir = L.dir.as<uint32_t>();
+    const uint2 *p_pair = L.pair.as<const uint2>();
+    hipLaunchKernelGGL(toe_scatter_kernel, dim3(locate_grid(f.r)), dim3(kLocBlock), 0, nullptr, p_sel, p_end, f.r, p_toe);
+    hipLaunchKernelGGL(phi_dir_kernel, dim3(locate_grid(n_buckets + 1)), dim3(kLocBlock), 0, nullptr, p_pair, f.s, shift, n_buckets,
+                       p_dir);
+    TRY_HIP(hipGetLastError(), nullptr, msg);
+    TRY_HIP(hipDeviceSynchronize(), nullptr, msg);
+    L.shift = shift;
+    L.n_buckets = n_buckets;
+    L.doc_start.assign(f.doc_start, f.doc_start + f.n_docs);
+    return COLBWT_OK;
+}
+
 }  // namespace
 
 namespace {
@@ -780,7 +937,7 @@ int colbwt_index_info(const colbwt_index *idx, colbwt_info *out) {
     out->r = idx->ix.r();
     out->sigma = idx->ix.sigma();
     out->device = (uint32_t)idx->ix.device();
-    out->device_bytes = idx->ix.device_bytes();
+    out->device_bytes = idx->ix.device_bytes() + idx->loc.bytes();
     out->layout = (uint32_t)idx->ix.layout();
     out->layout_shape = idx->ix.line_rows() ? (idx->ix.table_fat().steps << 8) | kFatSlotSteps : 0;
     out->table_rows = idx->ix.table_rows();
@@ -829,10 +986,12 @@ int colbwt_query_device_ordered(colbwt_index *idx, const uint8_t *d_bases, const
 // out and writes the two result files -- so the wall time is the slowest stage's, not the sum.
 // Output bytes and order are those of the sequential loop.  `binary`: the container of
 // bin_writer.h instead of the reference's text.  `count`: count queries (count_query.h) instead,
-// one line per read "name\tm\tmlen\tocc\n" in pml_name (cid_name unused).
+// one line per read "name\tm\tmlen\tocc\n" in pml_name (cid_name unused).  `locate_k` > 0 (with
+// `count`): locate queries (locate_query.h) with max_occ = locate_k, the line followed by
+// "\tdoc:offset,doc:offset,..".
 static int query_file_impl(colbwt_index *idx, const char *pattern_path, const std::string &pml_name,
                            const std::string &cid_name, uint64_t batch_bases, colbwt_stats *stats, bool binary,
-                           bool count = false) {
+                           bool count = false, uint32_t locate_k = 0) {
     if (stats) memset(stats, 0, sizeof(*stats));
     const size_t replicas = 1 + idx->more.size();
     if (batch_bases == 0) batch_bases = (64ull << 20) * replicas;
@@ -923,9 +1082,20 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
             if (count) {
                 const uint32_t *ml = b->pml->as<uint32_t>();
                 const uint64_t *oc = b->cid->as<uint64_t>();
-                for (uint64_t k = 0; k < n_reads && count_ok; ++k)
-                    count_ok = fprintf(wn, "%s\t%llu\t%u\t%llu\n", b->names[k].c_str(),
+                const uint64_t *ps = oc + n_reads;          // locate: locate_k positions per read
+                const std::vector<uint64_t> &ds = idx->loc.doc_start;
+                for (uint64_t k = 0; k < n_reads && count_ok; ++k) {
+                    count_ok = fprintf(wn, locate_k ? "%s\t%llu\t%u\t%llu\t" : "%s\t%llu\t%u\t%llu\n", b->names[k].c_str(),
                                        (unsigned long long)(b->off[k + 1] - b->off[k]), ml[k], (unsigned long long)oc[k]) > 0;
+                    if (!locate_k) continue;
+                    const uint64_t want = std::min<uint64_t>(oc[k], locate_k);
+                    for (uint64_t t = 0; t < want && count_ok; ++t) {
+                        const uint64_t x = ps[k * locate_k + t];
+                        const size_t d = (size_t)(std::upper_bound(ds.begin(), ds.end(), x) - ds.begin()) - 1;
+                        count_ok = fprintf(wn, t ? ",%zu:%llu" : "%zu:%llu", d, (unsigned long long)(x - ds[d])) > 0;
+                    }
+                    count_ok = count_ok && fputc('\n', wn) != EOF;
+                }
                 t_format += now() - t0;
                 free_q.push(b);
                 continue;
@@ -962,11 +1132,14 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
         const double t0 = now();
         colbwt_stats st{};
         rc = select_device(idx->ix.device(), g_err);
-        if (rc == COLBWT_OK && count && (!b->pml->ensure(n_reads * 4) || !b->cid->ensure(n_reads * 8)))
+        if (rc == COLBWT_OK && count && (!b->pml->ensure(n_reads * 4) || !b->cid->ensure(n_reads * 8 * (1 + (uint64_t)locate_k))))
             rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
         if (rc == COLBWT_OK && !count && (!b->cid->ensure(nb) || !b->pml->ensure(nb * (b->wide ? 4 : 2))))
             rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
         if (rc != COLBWT_OK) {
+        } else if (locate_k) {
+            rc = locate_batch_all(idx, b->bases.data(), b->off.data(), n_reads, locate_k, b->pml->as<uint32_t>(), b->cid->as<uint64_t>(),
+                                  b->cid->as<uint64_t>() + n_reads, &st);
         } else if (count) {
             rc = count_batch_all(idx, b->bases.data(), b->off.data(), n_reads, b->pml->as<uint32_t>(), b->cid->as<uint64_t>(),
                                  nullptr, &st);
@@ -1048,6 +1221,91 @@ int colbwt_count_file(colbwt_index *idx, const char *pattern_path, const char *o
     if (!idx || !pattern_path) return fail(COLBWT_ERR_ARG, "null argument");
     const std::string out = out_path ? out_path : std::string(pattern_path) + ".count";
     return query_file_impl(idx, pattern_path, out, out, batch_bases, stats, false, true);
+}
+
+int colbwt_index_attach_locate_memory(colbwt_index *idx, const void *col_loc_bytes, uint64_t len) {
+    if (!idx || !col_loc_bytes) return fail(COLBWT_ERR_ARG, "null argument");
+    const uint8_t *p = (const uint8_t *)col_loc_bytes;
+    std::vector<uint32_t> aligned_copy;          // the u32 arrays are read in place
+    if ((uintptr_t)p & 3) {
+        aligned_copy.resize((len + 3) / 4);
+        memcpy(aligned_copy.data(), p, len);
+        p = (const uint8_t *)aligned_copy.data();
+    }
+    LocFile f;
+    std::string msg;
+    int rc = parse_loc(p, len, idx->ix, f, msg);
+    if (rc != COLBWT_OK) return fail(rc, msg);
+    std::vector<colbwt_index *> reps{idx};
+    reps.insert(reps.end(), idx->more.begin(), idx->more.end());
+    for (colbwt_index *rep : reps) {
+        rc = attach_one(rep, f, msg);
+        if (rc != COLBWT_OK) {
+            if (reps.size() > 1) msg = "device " + std::to_string(rep->ix.device()) + ": " + msg;
+            for (colbwt_index *x : reps) {   // all replicas or none
+                if (select_device(x->ix.device(), g_err) == COLBWT_OK) x->loc.reset();
+            }
+            return fail(rc, msg);
+        }
+    }
+    return COLBWT_OK;
+}
+
+int colbwt_index_attach_locate(colbwt_index *idx, const char *prefix_or_file) {
+    if (!idx || !prefix_or_file) return fail(COLBWT_ERR_ARG, "null argument");
+    MappedFile mf;
+    if (!mf.open(std::string(prefix_or_file) + ".col_loc") && !mf.open(prefix_or_file))
+        return fail(COLBWT_ERR_IO, std::string("cannot open ") + prefix_or_file + ".col_loc (or " + prefix_or_file + ")");
+    if (!mf.data) return fail(COLBWT_ERR_FORMAT, "empty .col_loc file");
+    return colbwt_index_attach_locate_memory(idx, mf.data, mf.len);
+}
+
+int colbwt_locate_docs(const colbwt_index *idx, uint64_t *doc_start, uint32_t cap, uint32_t *n_docs) {
+    if (!idx || !n_docs) return fail(COLBWT_ERR_ARG, "null argument");
+    if (!idx->loc.ready()) return fail(COLBWT_ERR_ARG, "no locate samples attached (colbwt_index_attach_locate)");
+    const std::vector<uint64_t> &ds = idx->loc.doc_start;
+    *n_docs = (uint32_t)ds.size();
+    if (!doc_start || cap < ds.size()) return fail(COLBWT_ERR_ARG, "doc_start holds fewer than n_docs entries");
+    std::copy(ds.begin(), ds.end(), doc_start);
+    return COLBWT_OK;
+}
+
+int colbwt_locate_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t max_occ,
+                        uint32_t *mlen, uint64_t *occ, uint64_t *pos, colbwt_stats *stats) {
+    return locate_batch_all(idx, bases, read_off, n_reads, max_occ, mlen, occ, pos, stats);
+}
+
+int colbwt_locate_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads,
+                         uint64_t n_bases, uint32_t max_occ, uint32_t *d_mlen, uint64_t *d_occ, uint64_t *d_pos,
+                         const uint32_t *d_order, void *hip_stream, colbwt_stats *stats) {
+    auto bad_argument = [&]() -> const char * {
+        if (max_occ == 0 || max_occ > kLocateMaxOcc) return "max_occ must be 1 .. 2^20";
+        if (!idx->loc.ready()) return "no locate samples attached (colbwt_index_attach_locate)";
+        for (colbwt_index *r : idx->more)
+            if (!r->loc.ready()) return "no locate samples attached (colbwt_index_attach_locate)";
+        if (n_reads == 0) return nullptr;
+        if (!d_bases || !d_read_off || !d_mlen || !d_occ || !d_pos) return "null device pointer";
+        if (((uintptr_t)d_bases & 15) || ((uintptr_t)d_mlen & 3) || ((uintptr_t)d_occ & 7) || ((uintptr_t)d_pos & 7))
+            return "d_bases must be 16-byte aligned, d_mlen 4-byte and d_occ/d_pos 8-byte aligned";
+        return nullptr;
+    };
+    return device_entry(idx, d_bases, n_reads, n_bases, hip_stream, 0, stats, bad_argument,
+                        [&](const Index &ix, hipStream_t stream) {
+                            const LocateTables &L = replica_for(idx, d_bases)->loc;
+                            launch_locate(ix, L.toe_row.as<uint32_t>(), L.phi(), d_bases, d_read_off, n_reads, max_occ, d_mlen,
+                                          d_occ, d_pos, d_order, stream);
+                        });
+}
+
+int colbwt_locate_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t max_occ,
+                       uint64_t batch_bases, colbwt_stats *stats) {
+    if (!idx || !pattern_path) return fail(COLBWT_ERR_ARG, "null argument");
+    if (max_occ == 0 || max_occ > kLocateMaxOcc) return fail(COLBWT_ERR_ARG, "max_occ must be 1 .. 2^20");
+    if (!idx->loc.ready()) return fail(COLBWT_ERR_ARG, "no locate samples attached (colbwt_index_attach_locate)");
+    const std::string out = out_path ? out_path : std::string(pattern_path) + ".locate";
+    if (batch_bases == 0)   // the default batch of the file query, cut so that max_occ slots per read stay ~tens of MB
+        batch_bases = std::max<uint64_t>(1ull << 20, (64ull << 20) * (1 + idx->more.size()) * 16 / std::max<uint32_t>(16, max_occ));
+    return query_file_impl(idx, pattern_path, out, out, batch_bases, stats, false, true, max_occ);
 }
 
 int colbwt_binary_to_text(const char *bin_path, int value_bytes, const char *text_path) {

@@ -34,6 +34,7 @@
 
 #include "../../include/colbwt.h"
 #include "dev_mem.h"
+#include "locate_samples.h"
 #include "rlbwt_build.h"
 
 namespace colbwt {
@@ -272,7 +273,7 @@ struct BudgetScope {
 }  // namespace
 
 int rlbwt_from_text(const uint8_t *text, uint64_t n, const uint64_t *doc_start, uint32_t n_docs, uint64_t min_mum,
-                    int device, RlbwtResult &out, std::string &err) {
+                    int device, RlbwtResult &out, std::string &err, bool locate) {
     if (!text || !doc_start || n < 2 || n_docs == 0) { err = "empty text or no documents"; return COLBWT_ERR_ARG; }
     if (n >= 0xffffffffull) { err = "text of " + std::to_string(n) + " characters: the suffix numbers are 32-bit"; return COLBWT_ERR_FORMAT; }
     if (n_docs > kMaxDocs) { err = "more than " + std::to_string(kMaxDocs) + " documents"; return COLBWT_ERR_FORMAT; }
@@ -387,6 +388,47 @@ int rlbwt_from_text(const uint8_t *text, uint64_t n, const uint64_t *doc_start, 
     RB_TRY(hipMemcpy(&r, d_groups.get(), 8, hipMemcpyDeviceToHost));
     clock.lap("rlbwt:   BWT, run starts");
 
+    // locate samples (locate_samples.h): the run flags and the spare suffix-array buffer are free here
+    out.has_locate = locate;
+    if (locate) {
+        DevPtr d_end;
+        if (no(d_end.alloc(4 * r))) { err = "out of device memory for the locate samples"; return COLBWT_ERR_NOMEM; }
+        uint32_t *p_end = d_end.as<uint32_t>();
+        hipLaunchKernelGGL(run_end_sa_kernel, dim3(grid_for(r)), dim3(kSampleBlock), 0, 0, d_sa_final, d_start, (uint64_t)r, n, p_end);
+        hipLaunchKernelGGL(phi_flags_kernel, dim3(grid), dim3(kSampleBlock), 0, 0, d_bwt, n, d_flag);
+        uint32_t *d_at = d_sa_spare;
+        tb = tmp_bytes;
+        RB_TRY(hipcub::DeviceSelect::Flagged(d_tmp.get(), tb, hipcub::CountingInputIterator<uint32_t>(0), d_flag, d_at,
+                                             d_groups.as<unsigned long long>(), (size_t)n));
+        unsigned long long s = 0;
+        RB_TRY(hipMemcpy(&s, d_groups.get(), 8, hipMemcpyDeviceToHost));
+        // s >= 1: the text's only 0 is a BWT byte of its own, at j = ISA[0] >= 1 (SA[0] = n - 1)
+        DevPtr d_pk[2], d_pv[2], extra;
+        if (no(d_pk[0].alloc(4 * s)) || no(d_pk[1].alloc(4 * s)) || no(d_pv[0].alloc(4 * s)) || no(d_pv[1].alloc(4 * s))) {
+            err = "out of device memory for the locate samples";
+            return COLBWT_ERR_NOMEM;
+        }
+        hipcub::DoubleBuffer<uint32_t> pk(d_pk[0].as<uint32_t>(), d_pk[1].as<uint32_t>()), pv(d_pv[0].as<uint32_t>(), d_pv[1].as<uint32_t>());
+        uint32_t *k0 = pk.Current(), *v0 = pv.Current();
+        hipLaunchKernelGGL(phi_pairs_kernel, dim3(grid_for(s)), dim3(kSampleBlock), 0, 0, d_sa_final, d_at, (uint64_t)s, k0, v0);
+        size_t sb = 0;
+        RB_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sb, pk, pv, (size_t)s, 0, bits));
+        void *ws = d_tmp.get();
+        if (sb > tmp_bytes) {
+            if (no(extra.alloc(sb))) { err = "out of device memory (sample sort workspace)"; return COLBWT_ERR_NOMEM; }
+            ws = extra.get();
+        }
+        RB_TRY(hipcub::DeviceRadixSort::SortPairs(ws, sb, pk, pv, (size_t)s, 0, bits));
+        out.end_sa.resize(r);
+        out.phi_pos.resize(s);
+        out.phi_val.resize(s);
+        RB_TRY(hipMemcpy(out.end_sa.data(), p_end, 4 * r, hipMemcpyDeviceToHost));
+        RB_TRY(hipMemcpy(out.phi_pos.data(), pk.Current(), 4 * s, hipMemcpyDeviceToHost));
+        RB_TRY(hipMemcpy(out.phi_val.data(), pv.Current(), 4 * s, hipMemcpyDeviceToHost));
+        out.doc_start.assign(doc_start, doc_start + n_docs);
+        clock.lap("rlbwt:   locate samples");
+    }
+
     // thresholds
     DevPtr d_head, d_head2, d_id, d_id2, d_thr;
     if (no(d_head.alloc(r)) || no(d_head2.alloc(r)) || no(d_id.alloc(4 * r)) || no(d_id2.alloc(4 * r)) || no(d_thr.alloc(4 * r))) {
@@ -491,20 +533,30 @@ thread_local std::string g_rlbwt_err;
 
 extern "C" const char *colbwt_rlbwt_error(void) { return g_rlbwt_err.c_str(); }
 
-extern "C" int colbwt_rlbwt_build_text(const uint8_t *text, uint64_t n, const uint64_t *doc_start, uint32_t n_docs,
-                                       uint64_t min_mum, int device, colbwt_rlbwt **out) {
+static int build_text(const uint8_t *text, uint64_t n, const uint64_t *doc_start, uint32_t n_docs, uint64_t min_mum, int device,
+                      colbwt_rlbwt **out, bool locate) {
     if (!out) { g_rlbwt_err = "null argument"; return COLBWT_ERR_ARG; }
     *out = nullptr;
     colbwt_rlbwt *h = new colbwt_rlbwt;
     h->n_docs = n_docs;
-    const int rc = colbwt::rlbwt_from_text(text, n, doc_start, n_docs, min_mum, device, h->res, g_rlbwt_err);
+    const int rc = colbwt::rlbwt_from_text(text, n, doc_start, n_docs, min_mum, device, h->res, g_rlbwt_err, locate);
     if (rc != COLBWT_OK) { delete h; return rc; }
     *out = h;
     return COLBWT_OK;
 }
 
-extern "C" int colbwt_rlbwt_build_files(const char *const *fastas, uint32_t n_files, int revcomp, uint64_t min_mum, int device,
-                                        const char *out_prefix, colbwt_rlbwt **out) {
+extern "C" int colbwt_rlbwt_build_text(const uint8_t *text, uint64_t n, const uint64_t *doc_start, uint32_t n_docs,
+                                       uint64_t min_mum, int device, colbwt_rlbwt **out) {
+    return build_text(text, n, doc_start, n_docs, min_mum, device, out, false);
+}
+
+extern "C" int colbwt_rlbwt_build_text_locate(const uint8_t *text, uint64_t n, const uint64_t *doc_start, uint32_t n_docs,
+                                              uint64_t min_mum, int device, colbwt_rlbwt **out) {
+    return build_text(text, n, doc_start, n_docs, min_mum, device, out, true);
+}
+
+static int build_files(const char *const *fastas, uint32_t n_files, int revcomp, uint64_t min_mum, int device,
+                       const char *out_prefix, colbwt_rlbwt **out, bool locate) {
     if (out) *out = nullptr;
     if (!fastas || !n_files || (!out_prefix && !out)) { g_rlbwt_err = "null argument"; return COLBWT_ERR_ARG; }
     std::vector<std::string> paths;
@@ -519,12 +571,30 @@ extern "C" int colbwt_rlbwt_build_files(const char *const *fastas, uint32_t n_fi
     clock.lap("rlbwt: FASTA files read");
     colbwt_rlbwt *h = new colbwt_rlbwt;
     h->n_docs = n_files;
-    int rc = colbwt::rlbwt_from_text(text.data(), text.size(), doc_start.data(), n_files, min_mum, device, h->res, g_rlbwt_err);
+    int rc = colbwt::rlbwt_from_text(text.data(), text.size(), doc_start.data(), n_files, min_mum, device, h->res, g_rlbwt_err, locate);
     clock.lap("rlbwt: construction");
     if (rc == COLBWT_OK && out_prefix && !colbwt::write_rlbwt_files(out_prefix, h->res, n_files, g_rlbwt_err)) rc = COLBWT_ERR_IO;
+    if (rc == COLBWT_OK && out_prefix && locate && !colbwt::write_locate_file(std::string(out_prefix) + ".col_loc", h->res, g_rlbwt_err))
+        rc = COLBWT_ERR_IO;
     clock.lap("rlbwt: files written");
     if (rc != COLBWT_OK || !out) delete h; else *out = h;
     return rc;
+}
+
+extern "C" int colbwt_rlbwt_build_files(const char *const *fastas, uint32_t n_files, int revcomp, uint64_t min_mum, int device,
+                                        const char *out_prefix, colbwt_rlbwt **out) {
+    return build_files(fastas, n_files, revcomp, min_mum, device, out_prefix, out, false);
+}
+
+extern "C" int colbwt_rlbwt_build_files_locate(const char *const *fastas, uint32_t n_files, int revcomp, uint64_t min_mum,
+                                               int device, const char *out_prefix, colbwt_rlbwt **out) {
+    return build_files(fastas, n_files, revcomp, min_mum, device, out_prefix, out, true);
+}
+
+extern "C" int colbwt_rlbwt_write_locate(const colbwt_rlbwt *h, const char *path) {
+    if (!h || !path) { g_rlbwt_err = "null argument"; return COLBWT_ERR_ARG; }
+    if (!h->res.has_locate) { g_rlbwt_err = "built without locate samples"; return COLBWT_ERR_ARG; }
+    return colbwt::write_locate_file(path, h->res, g_rlbwt_err) ? COLBWT_OK : COLBWT_ERR_IO;
 }
 
 extern "C" void colbwt_rlbwt_get(const colbwt_rlbwt *h, colbwt_rlbwt_view *v) {

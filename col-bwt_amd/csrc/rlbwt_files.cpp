@@ -119,4 +119,34 @@ bool write_rlbwt_files(const std::string &prefix, const RlbwtResult &res, uint32
     return ok;
 }
 
+bool write_locate_file(const std::string &path, const RlbwtResult &res, std::string &err) {
+    const uint64_t r = res.end_sa.size(), s = res.phi_pos.size();
+    const uint32_t n_docs = (uint32_t)res.doc_start.size(), version = 1;
+    std::vector<uint8_t> buf(40 + 4 * r + 8 * s + 4 * (uint64_t)n_docs);
+    uint8_t *p = buf.data();
+    memcpy(p, "COLBWTLC", 8);
+    memcpy(p + 8, &version, 4);
+    memcpy(p + 12, &n_docs, 4);
+    memcpy(p + 16, &res.n, 8);
+    memcpy(p + 24, &r, 8);
+    memcpy(p + 32, &s, 8);
+    p += 40;
+    memcpy(p, res.end_sa.data(), 4 * r);
+    p += 4 * r;
+    for (uint64_t i = 0; i < s; ++i) {
+        memcpy(p + 8 * i, &res.phi_pos[i], 4);
+        memcpy(p + 8 * i + 4, &res.phi_val[i], 4);
+    }
+    p += 8 * s;
+    for (uint32_t d = 0; d < n_docs; ++d) {
+        const uint32_t v = (uint32_t)res.doc_start[d];
+        memcpy(p + 4 * d, &v, 4);
+    }
+    if (!write_all(path, buf.data(), buf.size())) {
+        err = "cannot write " + path;
+        return false;
+    }
+    return true;
+}
+
 }  // namespace colbwt

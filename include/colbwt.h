@@ -58,7 +58,7 @@ typedef struct colbwt_info {
     uint64_t r;            /* rows (sub-runs)       (LF_table.hpp:361) */
     uint32_t sigma;        /* distinct characters present in the table */
     uint32_t device;       /* HIP device ordinal                       */
-    uint64_t device_bytes; /* HBM held by the index                    */
+    uint64_t device_bytes; /* HBM held by the index (locate samples included) */
     uint32_t layout;       /* COLBWT_LAYOUT_ONE_STEP / _TWO_ / _THREE_ / _LINE_ROWS / _MISMATCH_LINES[_DEEP] */
     uint32_t layout_shape; /* line rows: own steps << 8 | steps per mismatch slot; else 0 */
     uint64_t table_rows;   /* rows of the HBM table actually queried   */
@@ -236,6 +236,49 @@ int colbwt_count_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_
 int colbwt_count_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint64_t batch_bases,
                       colbwt_stats *stats);
 
+/* ---- locate: text positions of each read's longest exact match ----------------------------
+ * The backward search of colbwt_count_* with one exception: a read byte <= 1 ends the search (the
+ * folded separator / terminator class, where the table's LF is not the text's).  On reads without
+ * such a byte mlen and occ equal count's.  With k = min(occ, max_occ), the read's max_occ result
+ * slots hold SA[ep], SA[ep-1], .., SA[ep-k+1]: the start positions in the indexed text of
+ * occurrences of P[m-mlen..m), in suffix-array order from the range's last suffix down; the slots
+ * past k hold COLBWT_LOCATE_NONE.  There is no "all occurrences" mode.
+ *
+ * Samples: <prefix>.col_loc, written by the builder (colbwt_rlbwt_build_files_locate, build_rlbwt -L,
+ * col-bwt build --locate); they cannot be rebuilt from a .col_pml.  Little-endian:
+ *   header   u8 magic[8] "COLBWTLC" | u32 version = 1 | u32 n_docs | u64 n | u64 r | u64 s  (40 bytes)
+ *   end_sa   u32[r]    SA at the last position of every folded run (bytes <= 1 one character, as in
+ *                      .bwt.heads), in BWT order: r = the .col_pml's bwt_r
+ *   phi      u32[2s]   pairs (SA[j], SA[j-1]) for every j >= 1 where the UNFOLDED BWT byte changes
+ *                      (0 and 1 distinct), sorted by SA[j]; SA[j] = 0 is always among them
+ *   docs     u32[n_docs]  doc_start: first text position of every document
+ * phi(x) = SA[ISA[x]-1] = val(a) + (x - a) for a = the largest sampled position <= x.
+ *
+ * colbwt_index_attach_locate(_memory) loads the samples onto every replica of an open index (prefix +
+ * ".col_loc", else the path itself).  It checks n and r against the table, that the table has exactly
+ * r rows ending a run (the next row holds another character, or it is the last row), every value
+ * < n and ascending phi positions.  HBM: 4 bytes per row of the layout in HBM + 12 to 16 bytes per
+ * phi sample.  On failure no replica keeps samples; the index still answers query and count.
+ * colbwt_locate_docs copies doc_start (cap entries of room; *n_docs receives their number).
+ *
+ * Entry points as colbwt_count_batch / colbwt_count_device (sharding over replicas, d_order,
+ * alignment: d_pos 8-byte aligned), with max_occ in 1 .. 2^20 and pos / d_pos holding
+ * n_reads * max_occ u64 slots (read k: [k * max_occ, (k+1) * max_occ)).
+ * colbwt_locate_file: one text line per read "name\tm\tmlen\tocc\tdoc:offset,doc:offset,..\n"
+ * (doc = 0-based document number in build order, offset = position - doc_start[doc]; the last field
+ * is empty when occ == 0), out_path NULL => pattern + ".locate". */
+#define COLBWT_LOCATE_NONE (~(uint64_t)0)
+int colbwt_index_attach_locate(colbwt_index *idx, const char *prefix_or_file);
+int colbwt_index_attach_locate_memory(colbwt_index *idx, const void *col_loc_bytes, uint64_t len);
+int colbwt_locate_docs(const colbwt_index *idx, uint64_t *doc_start, uint32_t cap, uint32_t *n_docs);
+int colbwt_locate_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t max_occ,
+                        uint32_t *mlen, uint64_t *occ, uint64_t *pos, colbwt_stats *stats);
+int colbwt_locate_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads,
+                         uint64_t n_bases, uint32_t max_occ, uint32_t *d_mlen, uint64_t *d_occ, uint64_t *d_pos,
+                         const uint32_t *d_order, void *hip_stream, colbwt_stats *stats);
+int colbwt_locate_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t max_occ,
+                       uint64_t batch_bases, colbwt_stats *stats);
+
 /* ---- index construction (SURVEY.md 8(f) "next" #1) ------------------------ */
 
 /* build_col_bwt <prefix> (src/build_col_bwt.cpp:14-52): reads <prefix>.bwt.heads,
@@ -323,6 +366,15 @@ int colbwt_rlbwt_build_text(const uint8_t *text, uint64_t n, const uint64_t *doc
  * hands the result back when `out` is not NULL. */
 int colbwt_rlbwt_build_files(const char *const *fastas, uint32_t n_files, int revcomp, uint64_t min_mum, int device,
                              const char *out_prefix, colbwt_rlbwt **out);
+/* The same builds that also gather the locate samples (colbwt_locate_*) on the device: end_sa at the
+ * run ends and the phi pairs, sorted by position.  _files writes <out_prefix>.col_loc beside the
+ * four files; colbwt_rlbwt_write_locate writes the .col_loc of a handle built by either (ERR_ARG for
+ * a handle built without samples). */
+int colbwt_rlbwt_build_text_locate(const uint8_t *text, uint64_t n, const uint64_t *doc_start, uint32_t n_docs,
+                                   uint64_t min_mum, int device, colbwt_rlbwt **out);
+int colbwt_rlbwt_build_files_locate(const char *const *fastas, uint32_t n_files, int revcomp, uint64_t min_mum, int device,
+                                    const char *out_prefix, colbwt_rlbwt **out);
+int colbwt_rlbwt_write_locate(const colbwt_rlbwt *h, const char *path);
 void colbwt_rlbwt_get(const colbwt_rlbwt *h, colbwt_rlbwt_view *view);   /* pointers live until _free */
 void colbwt_rlbwt_free(colbwt_rlbwt *h);
 const char *colbwt_rlbwt_error(void);
