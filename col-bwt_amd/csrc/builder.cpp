@@ -65,6 +65,12 @@ extern "C" int colbwt_build_col_pml_arrays(const uint8_t *heads, uint64_t n_head
     // strictly inside a run; its id is the id of the last split bit at or before
     // its start (ids are consumed one per split bit, col_bwt.hpp:177-181,197-199;
     // 0 before the first bit; the last value persists when .col_ids runs out).
+    // Unlike the reference, no row is longer than kMaxRowLen: the offset field is
+    // 16 bits (LF_table.hpp:39), and a row's F start that lies deeper than 65535
+    // into a longer row would be cut (a homopolymer or N stretch of > 64 kbp gives
+    // such a run).  The extra pieces keep the run's character, id and threshold
+    // group, so LF, PML and col ids are those of the unsplit run.
+    constexpr uint64_t kMaxRowLen = 1ull << 16;
     std::vector<SubRun> rows;
     rows.reserve(n_heads + n_splits);
     uint64_t n = 0, bwt_r = 0, s = 0, ids_used = 0;
@@ -72,6 +78,11 @@ extern "C" int colbwt_build_col_pml_arrays(const uint8_t *heads, uint64_t n_head
     auto consume_split = [&]() {
         if (ids_used < n_ids) cur_id = col_ids[ids_used++];
         ++s;
+    };
+    auto emit = [&](uint64_t at, uint64_t len, uint8_t ch) {
+        uint64_t k = 0;
+        do rows.push_back({at + k, ch, cur_id});   // at least one row, as the reference
+        while ((k += kMaxRowLen) < len);
     };
     for (uint64_t h = 0; h < n_heads; ++h) {
         const uint8_t b = heads[h];
@@ -82,13 +93,13 @@ extern "C" int colbwt_build_col_pml_arrays(const uint8_t *heads, uint64_t n_head
         const uint64_t run_end = n + len;
         if (s < n_splits && split_pos[s] == n) consume_split();   // :177-181
         while (s < n_splits && split_pos[s] < run_end) {
-            rows.push_back({n, ch, cur_id});
+            emit(n, split_pos[s] - n, ch);
             len -= split_pos[s] - n;
             n = split_pos[s];
             consume_split();
         }
         if (len > 0) {
-            rows.push_back({n, ch, cur_id});
+            emit(n, len, ch);
             n += len;
         }
         ++bwt_r;

@@ -434,7 +434,13 @@ uint64_t oracle_build_col_pml(const uint8_t *heads, uint64_t n_heads, const uint
                               uint8_t *out, uint64_t out_cap)
 {
     /* col_bwt(heads, lengths, col_ids, splits), col_bwt.hpp:124-230 */
-    uint64_t cap = n_heads + n_splits + 1, nrows = 0;
+    /* One deliberate departure from the reference: no row is longer than ORACLE_MAX_ROW_LEN.  The
+     * offset bit-field is 16 bits (LF_table.hpp:39, :376), so a row whose F start lies deeper than
+     * 65535 into a longer row would get a cut offset (a homopolymer or N stretch of > 64 kbp makes
+     * such a run).  The pieces keep the run's character, id and threshold group. */
+    uint64_t total_len = 0;
+    for (uint64_t h = 0; h < n_heads; ++h) total_len += lens[h];
+    uint64_t cap = n_heads + n_splits + total_len / ORACLE_MAX_ROW_LEN + 1, nrows = 0;
     brow *rows = (brow *)calloc(cap, sizeof(brow));
     uint64_t s_set_bits = n_splits;                               /* :141-142 */
     uint64_t n = 0, bwt_r = 0, s = 0, id_pos = 0;                 /* :158-163 */
@@ -442,6 +448,9 @@ uint64_t oracle_build_col_pml(const uint8_t *heads, uint64_t n_heads, const uint
     uint64_t curr_id = 0;                                         /* :166 */
 #define SELECT_NEXT() ((s < s_set_bits) ? split_pos[s] : 0)       /* s_select(s + 1), else 0 (:180,:198) */
 #define READ_ID() do { if (id_pos < n_ids) curr_id = col_ids[id_pos++]; } while (0) /* 1 byte into a zeroed size_t */
+#define EMIT_ROWS(at, len) do { uint64_t k_ = 0; do { /* at least one row, as the reference */ \
+        rows[nrows].c = (uint8_t)c; rows[nrows].idx = (at) + k_; rows[nrows].id = curr_id; ++nrows; \
+        k_ += ORACLE_MAX_ROW_LEN; } while (k_ < (len)); } while (0)
     for (uint64_t h = 0; h < n_heads; ++h) {                      /* :167 while ((c = heads.get()) != EOF) */
         signed char c = (signed char)heads[h];
         if (c == (signed char)EOF) break;                         /* char 0xFF compares equal to EOF */
@@ -454,8 +463,8 @@ uint64_t oracle_build_col_pml(const uint8_t *heads, uint64_t n_heads, const uint
             s_curr = SELECT_NEXT();
         }
         while (s < s_set_bits && s_curr < run_end) {              /* :183 */
-            rows[nrows].c = (uint8_t)c; rows[nrows].idx = n; rows[nrows].id = curr_id; ++nrows;  /* :184-185 */
             uint64_t delta = s_curr - n;                          /* :186 */
+            EMIT_ROWS(n, delta);                                  /* :184-185 */
             n += delta;                                           /* :187 */
             length -= delta;                                      /* :188 */
             ++s;                                                  /* :197 */
@@ -463,7 +472,7 @@ uint64_t oracle_build_col_pml(const uint8_t *heads, uint64_t n_heads, const uint
             READ_ID();                                            /* :199 */
         }
         if (length > 0) {                                         /* :202 */
-            rows[nrows].c = (uint8_t)c; rows[nrows].idx = n; rows[nrows].id = curr_id; ++nrows;  /* :203-204 */
+            EMIT_ROWS(n, length);                                 /* :203-204 */
             n += length;                                          /* :205 */
         }
         ++bwt_r;                                                  /* :214 */
@@ -471,6 +480,7 @@ uint64_t oracle_build_col_pml(const uint8_t *heads, uint64_t n_heads, const uint
     uint64_t r = nrows;                                           /* :216 */
 #undef SELECT_NEXT
 #undef READ_ID
+#undef EMIT_ROWS
 
     /* LF_table::compute_table, LF_table.hpp:365-387: L_block_indices[c] lists the rows
      * holding c in row order; the outer loop runs over c ascending. */

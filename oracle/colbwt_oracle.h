@@ -30,6 +30,7 @@ extern "C" {
  * BWT_BYTES 5, RUN_BYTES 4, LEN_BYTES 2; DNA_ALPHABET off => 8-bit chars). */
 #define ORACLE_ROW_BYTES 18u   /* sizeof(col_thr), packed: col_bwt.hpp:81-115 */
 #define ORACLE_HEADER_BYTES 32u
+#define ORACLE_MAX_ROW_LEN 65536u  /* builder: longest row, so that every offset fits LEN_BITS = 16 */
 
 typedef struct oracle_index {
     uint64_t bwt_r;        /* col_bwt.hpp:383  */

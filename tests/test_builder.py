@@ -104,3 +104,49 @@ def test_agrees_with_python_true_bwt_pipeline(pkg, oracle):
     built = pkg.build_col_pml_arrays(heads, lens, t["cid"], splits, t["thr"][heads_mask])
     assert built.tobytes() == bytes(image)
     assert oracle.build_col_pml(heads, lens, t["cid"], splits, t["thr"][heads_mask]).tobytes() == bytes(image)
+
+
+def _lf_fields(image):
+    """(char, idx, interval, offset) of every row of a .col_pml image."""
+    n, r = struct.unpack_from("<QQ", image, 8)
+    rows = np.frombuffer(image, np.uint8, r * 18, 32).reshape(r, 18).astype(np.uint64)
+    le = lambda a, b: sum(rows[:, a + k] << np.uint64(8 * k) for k in range(b - a))  # noqa: E731
+    return rows[:, 0], le(1, 6), le(6, 10), le(10, 12), int(n)
+
+
+def test_runs_longer_than_the_offset_field(pkg, oracle):
+    """A BWT run of 70000 A's (a homopolymer): the row after it in F order starts 69998 positions into
+    it, more than the 16-bit offset field holds.  Both builders cut long runs into rows of at most
+    65536, so every row's (interval, offset) is its true F start, and a backward search over the image
+    counts the homopolymer's occurrences."""
+    import sys
+    import count_restatement
+    import sa_reference
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
+    import rlbwt_oracle
+    rng = np.random.default_rng(1)
+    s = rng.choice(np.frombuffer(b"ACGT", np.uint8), size=3000).tobytes()
+    text, starts = rlbwt_oracle.build_text([[s[:1000] + b"A" * 70000 + s[1000:]], [s]])
+    ref = sa_reference.build(text, starts)
+    heads, lens = ref["heads"].astype(np.uint8), ref["lens"].astype(np.uint64)
+    assert int(lens.max()) > 65536 * 1.05
+    split = ref["starts"].astype(np.uint64)
+    img = pkg.build_col_pml_arrays(heads, lens, np.zeros(heads.size, np.uint8), split, ref["thr"].astype(np.uint64))
+    assert img.tobytes() == oracle.build_col_pml(heads, lens, np.zeros(heads.size, np.uint8), split,
+                                                 ref["thr"].astype(np.uint64)).tobytes()
+    ch, idx, interval, offset, n = _lf_fields(img.tobytes())
+    assert n == len(text) and ch.size > heads.size
+    length = np.diff(np.append(idx, np.uint64(n)))
+    assert int(length.max()) <= 65536
+    # F start of every row: C[c] + the positions of c in the rows before it
+    f_start = np.zeros(ch.size, np.uint64)
+    acc = 0
+    for c in range(256):
+        rows_c = np.flatnonzero(ch == c)
+        f_start[rows_c] = acc + np.concatenate(([0], np.cumsum(length[rows_c])[:-1])).astype(np.uint64)
+        acc += int(length[rows_c].sum())
+    assert np.array_equal(idx[interval.astype(np.int64)] + offset, f_start)
+    t = count_restatement.Table(img)
+    loc = sa_reference.Locator(text, ref["sa"])
+    for rd in (b"A" * 30, b"A" * 1000, b"A" * 69000, s[990:1000] + b"A" * 50, b"A" * 50 + s[1000:1010]):
+        assert t.count(rd) == loc.count(rd), rd[:20]
