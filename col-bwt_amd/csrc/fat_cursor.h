@@ -172,7 +172,9 @@ void launch_persistent(const Table &T, const uint8_t *d_bases, const uint64_t *d
     const uint64_t avg_len = std::max<uint64_t>(n_bases / std::max<uint64_t>(n_reads, 1), 1);
     uint32_t big = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(n_bases / lanes / 6 / avg_len, 1), 8);
     uint32_t tail_permille = 100;
-    if (const char *e = getenv("COLBWT_LINE_ROWS_CHUNK")) {   // experiments: "<big>[,<tail permille>]"
+    // "<big>[,<tail permille>]": A/B experiments, and the tests' way into multi-read chunks at small batch
+    // sizes (tests/emu/chunk_emu.py, tests/test_gpu_chunks.py depend on it); values outside the ranges are ignored
+    if (const char *e = getenv("COLBWT_LINE_ROWS_CHUNK")) {
         const int v = atoi(e);
         if (v >= 1 && v <= 1024) big = (uint32_t)v;
         if (const char *c = strchr(e, ',')) tail_permille = (uint32_t)std::min(1000, std::max(0, atoi(c + 1)));

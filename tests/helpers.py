@@ -326,3 +326,98 @@ def position_hash_reference(values, extra=None, start=0):
         x = ((x ^ (x >> 27)) * (_H_M2 & _M64)) & _M64
         total += x ^ (x >> 31)
     return total & _M64
+
+
+# ---- ragged batches, vectorised (no Python loop per read)
+# Read lengths at the edges of the query kernels' machinery: empty and tiny reads, the 8-base trip
+# and 16-byte store piece, the 64-element output block, the collector's capacity of 96 elements
+# (csrc/lane_out.h), two blocks, and a read of a few blocks.
+EDGE_LENGTHS = (0, 1, 2, 7, 8, 9, 15, 16, 17, 63, 64, 65, 95, 96, 97, 127, 128, 129, 200)
+
+
+def ragged_lengths(rng, n_reads, n_long=0, long_range=(300, 1000), edges=EDGE_LENGTHS, weights=None):
+    """n_reads lengths drawn from `edges` (uniformly, or in proportion to `weights`), n_long of
+    them replaced by lengths from `long_range` (inclusive)."""
+    w = None if weights is None else np.asarray(weights, float) / np.sum(weights)
+    lens = rng.choice(np.asarray(edges, np.int64), size=n_reads, p=w)
+    if n_long:
+        lens[rng.choice(n_reads, size=n_long, replace=False)] = rng.integers(long_range[0], long_range[1] + 1, size=n_long)
+    return lens
+
+
+def ragged_reads(source, lens, rng, sub_rate=0.02, junk_fraction=0.35, junk_alphabet=b"ACGTN\x01", sprinkle=b"", n_sprinkle=0):
+    """(bases, read_off) of len(lens) reads.  A read is a substring of `source` (a text, or a long
+    backward-walk read: match-heavy) with substitutions over ACGT at `sub_rate`; `junk_fraction` of
+    the reads are instead random over `junk_alphabet` (mismatch-heavy; N is absent from the index,
+    0x01 is the terminator); n_sprinkle bases anywhere in the batch become bytes of `sprinkle`.
+    Bytes <= 1 of `source` become 'A', as in reads_from_text."""
+    lens = np.asarray(lens, np.int64)
+    src = np.frombuffer(bytes(source), np.uint8)
+    off = np.zeros(len(lens) + 1, np.uint64)
+    off[1:] = np.cumsum(lens)
+    total = int(off[-1])
+    assert lens.max(initial=0) < len(src) < 2**31
+    start = (rng.random(len(lens)) * (len(src) - lens)).astype(np.int32)
+    at = np.repeat(start - off[:-1].astype(np.int64), lens)         # source position minus base index, per base
+    at += np.arange(total, dtype=np.int64)
+    bases = src[at]
+    del at
+    bases[bases <= 1] = ord("A")
+    mut = np.flatnonzero(rng.random(total, dtype=np.float32) < sub_rate)
+    bases[mut] = rng.choice(np.frombuffer(b"ACGT", np.uint8), size=len(mut))
+    junk = np.flatnonzero(np.repeat(rng.random(len(lens)) < junk_fraction, lens))
+    bases[junk] = rng.choice(np.frombuffer(junk_alphabet, np.uint8), size=len(junk))
+    if n_sprinkle:
+        bases[rng.integers(0, total, size=n_sprinkle)] = rng.choice(np.frombuffer(sprinkle, np.uint8), size=n_sprinkle)
+    return bases, off
+
+
+# ---- the persistent lanes' chunk plan (csrc/fat_cursor.h), restated so that a test can say which
+# reads share a chunk and assert that the geometry it was written for is the one it gets
+QUERY_BLOCK = 256                    # csrc/query_kernels.h kQueryBlock
+
+
+def persistent_grid(n_reads, resident):
+    """Workgroups of a persistent query launch (launch_persistent): one per 256 reads until the
+    `resident` workgroups of the device are all there."""
+    return min(-(-n_reads // QUERY_BLOCK), resident)
+
+
+def chunk_setting(text):
+    """(big, tail permille) that COLBWT_LINE_ROWS_CHUNK=`text` selects: "<big>[,<tail permille>]"."""
+    head, _, tail = text.partition(",")
+    big, permille = int(head), int(tail) if tail else 100
+    assert 1 <= big <= 1024 and 0 <= permille <= 1000
+    return big, permille
+
+
+class ChunkPlan:
+    """ChunkPlan::init / first_read / last_read for workgroup `block` of `grid`: chunks [0, n_big)
+    hold `big` consecutive reads each, chunks [n_big, n_chunks) one read each."""
+
+    def __init__(self, n_reads, grid, block, big, tail_permille):
+        rem = n_reads % grid
+        self.read_lo = n_reads // grid * block + min(rem, block)
+        self.n = n_reads // grid + (1 if block < rem else 0)         # the share
+        tail = min(max(self.n * tail_permille // 1000, 2 * QUERY_BLOCK), self.n)
+        self.big = big
+        self.n_big = (self.n - tail) // big
+        self.n_chunks = self.n_big + (self.n - self.n_big * big)
+
+    def first_read(self, c):
+        return self.read_lo + (c * self.big if c < self.n_big else self.n_big * self.big + (c - self.n_big))
+
+    def last_read(self, c):
+        return self.read_lo + ((c + 1) * self.big - 1 if c < self.n_big else self.n_big * self.big + (c - self.n_big))
+
+
+def chunk_plans(n_reads, resident, big, tail_permille):
+    """The plans of all workgroups of a launch; checks that they tile the batch."""
+    grid = persistent_grid(n_reads, resident)
+    plans = [ChunkPlan(n_reads, grid, b, big, tail_permille) for b in range(grid)]
+    at = 0
+    for p in plans:
+        assert p.read_lo == at and p.first_read(0) == at and p.last_read(p.n_chunks - 1) == at + p.n - 1
+        at += p.n
+    assert at == n_reads
+    return plans
