@@ -34,8 +34,12 @@ EXPORTS = (
     "colbwt_index_attach_locate", "colbwt_index_attach_locate_memory", "colbwt_locate_docs", "colbwt_locate_batch",
     "colbwt_locate_device", "colbwt_locate_file",
     "colbwt_rlbwt_build_text_locate", "colbwt_rlbwt_build_files_locate", "colbwt_rlbwt_write_locate",
+    "colbwt_seeds_reduce_device", "colbwt_seeds_batch", "colbwt_seeds_file",
 )
 
+SEED_NONE = 0xFFFFFFFF          # include/colbwt.h COLBWT_SEED_NONE: seed_pos of a slot past the read's min(n_seeds, max_seeds)
+# colbwt_seed_summary as a numpy record: one per read
+SEED_SUMMARY = np.dtype([(k, np.uint32) for k in ("n_seeds", "max_len", "cov", "resets", "n_col", "col_cov", "asc", "desc")])
 LOCATE_NONE = (1 << 64) - 1     # include/colbwt.h COLBWT_LOCATE_NONE: a position slot past the read's min(occ, max_occ)
 
 
@@ -127,6 +131,9 @@ def lib():
     L.colbwt_rlbwt_build_text_locate.argtypes = [vp, u64, vp, u32, u64, C.c_int, C.POINTER(vp)]
     L.colbwt_rlbwt_build_files_locate.argtypes = [C.POINTER(C.c_char_p), u32, C.c_int, u64, C.c_int, C.c_char_p, C.POINTER(vp)]
     L.colbwt_rlbwt_write_locate.argtypes = [vp, C.c_char_p]
+    L.colbwt_seeds_reduce_device.argtypes = [vp, i32, vp, vp, u64, u64, u32, u32, vp, vp, vp, vp, vp, C.POINTER(Stats)]
+    L.colbwt_seeds_batch.argtypes = [vp, vp, vp, u64, u32, u32, vp, vp, vp, vp, C.POINTER(Stats)]
+    L.colbwt_seeds_file.argtypes = [vp, C.c_char_p, C.c_char_p, u32, u32, u64, C.POINTER(Stats)]
     _lib = L
     return L
 
@@ -270,6 +277,49 @@ class ColPml:
                                        batch_bases, C.byref(st)))
         return st
 
+    # -- seeds: per-read PML peaks and chain summaries (include/colbwt.h colbwt_seeds_*) ------------
+    def seeds_batch(self, bases, read_off, min_len=16, max_seeds=16, want_seeds=True):
+        """Many reads -> (summary, seed_pos, seed_len, seed_cid, Stats): summary a SEED_SUMMARY record per
+        read; the slot arrays (n_reads, max_seeds), largest pos first, unused slots SEED_NONE / 0 / 0
+        (None each when not want_seeds).  Query and reduction run on the device."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        n_reads = max(read_off.size - 1, 0)
+        summary = np.zeros(n_reads, SEED_SUMMARY)
+        k = int(max_seeds)
+        pos = np.zeros((n_reads, max(k, 0)), np.uint32) if want_seeds else None
+        ln = np.zeros((n_reads, max(k, 0)), np.uint32) if want_seeds else None
+        sc = np.zeros((n_reads, max(k, 0)), np.uint8) if want_seeds else None
+        st = Stats()
+        _check(lib().colbwt_seeds_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n_reads, int(min_len), k,
+                                        summary.ctypes.data, *((a.ctypes.data if want_seeds else None) for a in (pos, ln, sc)),
+                                        C.byref(st)))
+        return summary, pos, ln, sc, st
+
+    def seeds(self, pattern, min_len=16, max_seeds=16):
+        """One read -> (summary dict, [(pos, len, id), ..] largest pos first)."""
+        p = np.frombuffer(bytes(pattern), dtype=np.uint8)
+        summary, pos, ln, sc, _ = self.seeds_batch(p, np.array([0, p.size], np.uint64), min_len, max_seeds)
+        k = min(int(summary["n_seeds"][0]), int(max_seeds))
+        return ({f: int(summary[f][0]) for f in SEED_SUMMARY.names},
+                [(int(pos[0, t]), int(ln[0, t]), int(sc[0, t])) for t in range(k)])
+
+    @staticmethod
+    def seeds_reduce_device(d_pml, d_cid, d_read_off, n_reads, n_bases, min_len, max_seeds, d_summary, d_seed_pos=None,
+                            d_seed_len=None, d_seed_cid=None, pml_bytes=2, stream=0, timed=False):
+        """The reduction alone over device buffers a query_device call filled (raw device pointers, ints);
+        needs no index.  The three slot arrays may all be None."""
+        return seeds_reduce_device(d_pml, d_cid, d_read_off, n_reads, n_bases, min_len, max_seeds, d_summary, d_seed_pos,
+                                   d_seed_len, d_seed_cid, pml_bytes, stream, timed)
+
+    def seeds_file(self, pattern_path, out_path=None, min_len=16, max_seeds=16, batch_bases=0):
+        """FASTA/FASTQ(.gz) -> text lines "name\tm\tn_seeds\tcov\tmax_len\tresets\tn_col\tcol_cov\tasc\tdesc\tpos:len:id,.."
+        (default <pattern>.seeds)."""
+        st = Stats()
+        _check(lib().colbwt_seeds_file(self._h, os.fsencode(pattern_path), os.fsencode(out_path) if out_path else None,
+                                       int(min_len), int(max_seeds), batch_bases, C.byref(st)))
+        return st
+
     # -- locate (include/colbwt.h colbwt_locate_*) -------------------------------------------------
     def attach_locate(self, prefix_or_file=None, data=None):
         """Loads the locate samples onto every replica: <prefix>.col_loc (or the path itself), or a
@@ -375,6 +425,16 @@ def read_binary(bin_path, value_bytes):
         out.append((name, raw[at:at + m * value_bytes].view(dt)[::-1].copy()))
         at += m * value_bytes
     return out
+
+
+def seeds_reduce_device(d_pml, d_cid, d_read_off, n_reads, n_bases, min_len, max_seeds, d_summary, d_seed_pos=None,
+                        d_seed_len=None, d_seed_cid=None, pml_bytes=2, stream=0, timed=False):
+    """colbwt_seeds_reduce_device: pml / cid / read_off device arrays -> summaries and seed slots (device pointers, ints)."""
+    st = Stats()
+    _check(lib().colbwt_seeds_reduce_device(d_pml, pml_bytes, d_cid, d_read_off, n_reads, n_bases, int(min_len), int(max_seeds),
+                                            d_summary, d_seed_pos, d_seed_len, d_seed_cid, stream,
+                                            C.byref(st) if timed else None))
+    return st
 
 
 def pml_pack_device(d_pml, n_bases, d_mask, stream=0):

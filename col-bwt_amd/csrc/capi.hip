@@ -28,6 +28,7 @@
 #include "index.h"
 #include "locate_query.h"
 #include "query_kernels.h"
+#include "seeds_reduce.h"
 #include "text_writer.h"
 
 using namespace colbwt;
@@ -606,6 +607,62 @@ int locate_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *re
                          part);
 }
 
+// Largest max_seeds: results are n_reads x max_seeds slots of 9 bytes, in host memory and in HBM.
+constexpr uint32_t kSeedsMaxSeeds = 1u << 16;
+
+const char *seeds_bad_params(uint32_t min_len, uint32_t max_seeds) {
+    if (min_len == 0) return "min_len must be at least 1";
+    if (max_seeds == 0 || max_seeds > kSeedsMaxSeeds) return "max_seeds must be 1 .. 2^16";
+    return nullptr;
+}
+
+// Seeds (seeds_reduce.h) for a batch in host memory: the query and the reduction of its output run
+// back to back on the replica's stream; the per-base arrays never leave HBM.  The first result array
+// of the scratch holds pml (u16, or u32 when a read is longer than 65535), then cid; the second the
+// summaries, then the three slot arrays.
+int seeds_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t min_len,
+                    uint32_t max_seeds, uint32_t *summary, uint32_t *seed_pos, uint32_t *seed_len, uint8_t *seed_cid,
+                    colbwt_stats *stats) {
+    if (idx)
+        if (const char *m = seeds_bad_params(min_len, max_seeds)) return fail(COLBWT_ERR_ARG, m);
+    if (idx && n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, "more than 2^32-2 reads in a batch");
+    const bool slots = seed_pos != nullptr;
+    auto bad_pointers = [&](uint64_t n_bases) -> const char * {
+        if ((n_bases && !bases) || !summary) return "null bases/summary";
+        if ((seed_pos != nullptr) != (seed_len != nullptr) || (seed_pos != nullptr) != (seed_cid != nullptr))
+            return "seed_pos/seed_len/seed_cid: all three or none";
+        return nullptr;
+    };
+    auto part = [&](colbwt_index *rep, uint64_t lo, uint64_t hi, uint64_t max_len, uint64_t min_read, colbwt_stats *st,
+                    std::string &msg) {
+        const uint64_t n = hi - lo, off0 = read_off[lo], n_bases = read_off[hi] - off0;
+        const int pml_bytes = max_len > 65535 ? 4 : 2;
+        const uint64_t padded = (n_bases + 63) & ~63ull, n_slots = slots ? n * max_seeds : 0;
+        const uint64_t out_bytes[2] = {padded * (pml_bytes + 1) + 64, n * 32 + n_slots * 9};
+        auto launch = [&](const DeviceBatch &b) {
+            uint8_t *d_pml = (uint8_t *)b.out[0], *d_cid = d_pml + padded * pml_bytes;
+            uint32_t *d_sum = (uint32_t *)b.out[1], *d_pos = d_sum + n * 8, *d_len = d_pos + n_slots;
+            if (n_bases) launch_query(rep->ix, b.bases, b.off, n, n_bases, d_pml, pml_bytes, d_cid, b.order, b.stream);
+            (void)launch_seeds_reduce(d_pml, pml_bytes, d_cid, b.off, n, n_bases, min_len, max_seeds, d_sum, slots ? d_pos : nullptr,
+                                      slots ? d_len : nullptr, slots ? (uint8_t *)(d_len + n_slots) : nullptr, b.stream);
+        };
+        auto fetch = [&](const DeviceBatch &b) {
+            const uint32_t *d_sum = (const uint32_t *)b.out[1], *d_pos = d_sum + n * 8, *d_len = d_pos + n_slots;
+            TRY_HIP(hipMemcpyAsync(summary + lo * 8, d_sum, n * 32, hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            if (slots) {
+                TRY_HIP(hipMemcpyAsync(seed_pos + lo * max_seeds, d_pos, n_slots * 4, hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+                TRY_HIP(hipMemcpyAsync(seed_len + lo * max_seeds, d_len, n_slots * 4, hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+                TRY_HIP(hipMemcpyAsync(seed_cid + lo * max_seeds, d_len + n_slots, n_slots, hipMemcpyDeviceToHost, b.stream), b.stream,
+                        msg);
+            }
+            return COLBWT_OK;
+        };
+        return replica_batch(rep, bases + off0, read_off + lo, off0, n, max_len, min_read, pml_reads_order(rep->ix), out_bytes,
+                             kAlgBytesPerBase, st, msg, launch, fetch);
+    };
+    return sharded_batch(idx, read_off, n_reads, 0xFFFFFFFFull, "read longer than 2^32-1 bases", false, stats, bad_pointers, part);
+}
+
 // ---- .col_loc (include/colbwt.h): header, end_sa[r], phi pairs[s], doc_start[n_docs] ----
 constexpr uint64_t kLocHeader = 40;
 const char kLocMagic[8] = {'C', 'O', 'L', 'B', 'W', 'T', 'L', 'C'};
@@ -988,10 +1045,11 @@ int colbwt_query_device_ordered(colbwt_index *idx, const uint8_t *d_bases, const
 // bin_writer.h instead of the reference's text.  `count`: count queries (count_query.h) instead,
 // one line per read "name\tm\tmlen\tocc\n" in pml_name (cid_name unused).  `locate_k` > 0 (with
 // `count`): locate queries (locate_query.h) with max_occ = locate_k, the line followed by
-// "\tdoc:offset,doc:offset,..".
+// "\tdoc:offset,doc:offset,..".  `seeds_k` > 0 (with `count`): seeds (seeds_reduce.h) with min_len =
+// seeds_min and max_seeds = seeds_k, one line per read as colbwt_seeds_file documents it.
 static int query_file_impl(colbwt_index *idx, const char *pattern_path, const std::string &pml_name,
                            const std::string &cid_name, uint64_t batch_bases, colbwt_stats *stats, bool binary,
-                           bool count = false, uint32_t locate_k = 0) {
+                           bool count = false, uint32_t locate_k = 0, uint32_t seeds_min = 0, uint32_t seeds_k = 0) {
     if (stats) memset(stats, 0, sizeof(*stats));
     const size_t replicas = 1 + idx->more.size();
     if (batch_bases == 0) batch_bases = (64ull << 20) * replicas;
@@ -1079,6 +1137,26 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
             if (!b) break;
             const uint64_t n_reads = b->names.size();
             const double t0 = now();
+            if (seeds_k) {
+                const uint32_t *sm = b->pml->as<uint32_t>();           // 8 words per read
+                const uint32_t *sp = b->cid->as<uint32_t>(), *sl = sp + n_reads * seeds_k;
+                const uint8_t *sc = (const uint8_t *)(sl + n_reads * seeds_k);
+                for (uint64_t k = 0; k < n_reads && count_ok; ++k) {
+                    const uint32_t *q = sm + 8 * k;                    // n_seeds max_len cov resets n_col col_cov asc desc
+                    count_ok = fprintf(wn, "%s\t%llu\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t", b->names[k].c_str(),
+                                       (unsigned long long)(b->off[k + 1] - b->off[k]), q[0], q[2], q[1], q[3], q[4], q[5], q[6],
+                                       q[7]) > 0;
+                    const uint64_t want = std::min<uint64_t>(q[0], seeds_k);
+                    for (uint64_t t = 0; t < want && count_ok; ++t) {
+                        const uint64_t at = k * seeds_k + t;
+                        count_ok = fprintf(wn, t ? ",%u:%u:%u" : "%u:%u:%u", sp[at], sl[at], (unsigned)sc[at]) > 0;
+                    }
+                    count_ok = count_ok && fputc('\n', wn) != EOF;
+                }
+                t_format += now() - t0;
+                free_q.push(b);
+                continue;
+            }
             if (count) {
                 const uint32_t *ml = b->pml->as<uint32_t>();
                 const uint64_t *oc = b->cid->as<uint64_t>();
@@ -1132,11 +1210,17 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
         const double t0 = now();
         colbwt_stats st{};
         rc = select_device(idx->ix.device(), g_err);
-        if (rc == COLBWT_OK && count && (!b->pml->ensure(n_reads * 4) || !b->cid->ensure(n_reads * 8 * (1 + (uint64_t)locate_k))))
+        if (rc == COLBWT_OK && seeds_k && (!b->pml->ensure(n_reads * 32) || !b->cid->ensure(n_reads * 9 * (uint64_t)seeds_k)))
+            rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
+        if (rc == COLBWT_OK && count && !seeds_k && (!b->pml->ensure(n_reads * 4) || !b->cid->ensure(n_reads * 8 * (1 + (uint64_t)locate_k))))
             rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
         if (rc == COLBWT_OK && !count && (!b->cid->ensure(nb) || !b->pml->ensure(nb * (b->wide ? 4 : 2))))
             rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
         if (rc != COLBWT_OK) {
+        } else if (seeds_k) {
+            uint32_t *sp = b->cid->as<uint32_t>(), *sl = sp + n_reads * seeds_k;
+            rc = seeds_batch_all(idx, b->bases.data(), b->off.data(), n_reads, seeds_min, seeds_k, b->pml->as<uint32_t>(), sp, sl,
+                                 (uint8_t *)(sl + n_reads * seeds_k), &st);
         } else if (locate_k) {
             rc = locate_batch_all(idx, b->bases.data(), b->off.data(), n_reads, locate_k, b->pml->as<uint32_t>(), b->cid->as<uint64_t>(),
                                   b->cid->as<uint64_t>() + n_reads, &st);
@@ -1221,6 +1305,72 @@ int colbwt_count_file(colbwt_index *idx, const char *pattern_path, const char *o
     if (!idx || !pattern_path) return fail(COLBWT_ERR_ARG, "null argument");
     const std::string out = out_path ? out_path : std::string(pattern_path) + ".count";
     return query_file_impl(idx, pattern_path, out, out, batch_bases, stats, false, true);
+}
+
+int colbwt_seeds_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t min_len,
+                       uint32_t max_seeds, colbwt_seed_summary *summary, uint32_t *seed_pos, uint32_t *seed_len, uint8_t *seed_cid,
+                       colbwt_stats *stats) {
+    return seeds_batch_all(idx, bases, read_off, n_reads, min_len, max_seeds, (uint32_t *)summary, seed_pos, seed_len, seed_cid,
+                           stats);
+}
+
+int colbwt_seeds_reduce_device(const void *d_pml, int pml_bytes, const uint8_t *d_cid, const uint64_t *d_read_off, uint64_t n_reads,
+                               uint64_t n_bases, uint32_t min_len, uint32_t max_seeds, colbwt_seed_summary *d_summary,
+                               uint32_t *d_seed_pos, uint32_t *d_seed_len, uint8_t *d_seed_cid, void *hip_stream,
+                               colbwt_stats *stats) {
+    if (stats) memset(stats, 0, sizeof(*stats));
+    if (pml_bytes != 2 && pml_bytes != 4) return fail(COLBWT_ERR_ARG, "pml_bytes must be 2 or 4");
+    if (const char *m = seeds_bad_params(min_len, max_seeds)) return fail(COLBWT_ERR_ARG, m);
+    if (n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, "more than 2^32-2 reads in a batch");
+    if ((d_seed_pos != nullptr) != (d_seed_len != nullptr) || (d_seed_pos != nullptr) != (d_seed_cid != nullptr))
+        return fail(COLBWT_ERR_ARG, "d_seed_pos/d_seed_len/d_seed_cid: all three or none");
+    if (n_reads == 0) return COLBWT_OK;
+    if (!d_read_off || !d_summary || (n_bases && (!d_pml || !d_cid))) return fail(COLBWT_ERR_ARG, "null device pointer");
+    if (((uintptr_t)d_pml & 15) || ((uintptr_t)d_cid & 7) || ((uintptr_t)d_summary & 15) || ((uintptr_t)d_seed_pos & 3) ||
+        ((uintptr_t)d_seed_len & 3))
+        return fail(COLBWT_ERR_ARG, "d_pml/d_summary must be 16-byte aligned, d_cid 8-byte, d_seed_pos/d_seed_len 4-byte");
+    int n_dev = 0;
+    if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) {
+        (void)hipGetLastError();
+        return fail(COLBWT_ERR_NO_DEVICE, "no HIP device available (the query path has no CPU fallback)");
+    }
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    struct Events {
+        hipEvent_t e[2] = {nullptr, nullptr};
+        ~Events() {
+            for (hipEvent_t x : e)
+                if (x) (void)hipEventDestroy(x);
+        }
+    } ev;
+    if (stats) {
+        TRY_HIP(hipEventCreate(&ev.e[0]), nullptr, g_err);
+        TRY_HIP(hipEventCreate(&ev.e[1]), nullptr, g_err);
+        TRY_HIP(hipEventRecord(ev.e[0], stream), nullptr, g_err);
+    }
+    TRY_HIP(launch_seeds_reduce(d_pml, pml_bytes, d_cid, d_read_off, n_reads, n_bases, min_len, max_seeds, (uint32_t *)d_summary,
+                                d_seed_pos, d_seed_len, d_seed_cid, stream),
+            nullptr, g_err);
+    TRY_HIP(hipGetLastError(), nullptr, g_err);
+    if (stats) {
+        float ms = 0;
+        TRY_HIP(hipEventRecord(ev.e[1], stream), nullptr, g_err);
+        TRY_HIP(hipEventSynchronize(ev.e[1]), nullptr, g_err);
+        TRY_HIP(hipEventElapsedTime(&ms, ev.e[0], ev.e[1]), nullptr, g_err);
+        stats->n_reads = n_reads;
+        stats->n_bases = n_bases;
+        stats->kernel_ms = ms;
+    }
+    return COLBWT_OK;
+}
+
+int colbwt_seeds_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t min_len, uint32_t max_seeds,
+                      uint64_t batch_bases, colbwt_stats *stats) {
+    if (!idx || !pattern_path) return fail(COLBWT_ERR_ARG, "null argument");
+    if (const char *m = seeds_bad_params(min_len, max_seeds)) return fail(COLBWT_ERR_ARG, m);
+    const std::string out = out_path ? out_path : std::string(pattern_path) + ".seeds";
+    if (batch_bases == 0)   // the default batch of the file query, cut so that max_seeds slots per read stay ~tens of MB
+        batch_bases = std::max<uint64_t>(1ull << 20, (64ull << 20) * (1 + idx->more.size()) * 16 / std::max<uint32_t>(16, max_seeds));
+    return query_file_impl(idx, pattern_path, out, out, batch_bases, stats, false, true, 0, min_len, max_seeds);
 }
 
 int colbwt_index_attach_locate_memory(colbwt_index *idx, const void *col_loc_bytes, uint64_t len) {

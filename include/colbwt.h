@@ -279,6 +279,64 @@ int colbwt_locate_device(colbwt_index *idx, const uint8_t *d_bases, const uint64
 int colbwt_locate_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t max_occ,
                        uint64_t batch_bases, colbwt_stats *stats);
 
+/* ---- seeds: per-read PML peaks and chain summaries, reduced on the device -----------------
+ * What read classification consumes of a query's output, so that tens of bytes per read leave the
+ * device instead of 3 bytes per base.  The reference has no such mode; these semantics are this
+ * project's own.  Read P[0..m) has values pml[k] and cid[k] as colbwt_query_* produces them;
+ * parameters min_len >= 1 and max_seeds in 1 .. 2^16.
+ *   run      a maximal stretch [k, e) of consecutive bases of ONE read with pml >= 1 (runs never
+ *            cross a read boundary).  On a query's output e - k == pml[k]: PML counts up by one
+ *            towards smaller k and restarts at 0; the definition does not assume it.
+ *   seed     of a run: (pos = k, len = pml[k], id), id = cid[j] for the smallest j in [k, e) with
+ *            cid[j] != 0, else 0 -- the col id met closest to the peak, i.e. last in the order the
+ *            query computes.  A seed COUNTS when len >= min_len.
+ *   summary  per read, over ALL counting seeds (not only the stored ones):
+ *     n_seeds  number of counting seeds
+ *     max_len  largest pml value of the read, whatever min_len is
+ *     cov      sum of len over counting seeds
+ *     resets   number of bases with pml == 0
+ *     n_col    number of counting seeds with id != 0
+ *     col_cov  sum of len over counting seeds with id != 0
+ *     asc, desc  over pairs of counting seeds with id != 0 that are neighbours in read order: with a
+ *              the id at the smaller pos, b at the larger and d = (b - a + 255) % 255, d in 1..127
+ *              counts in asc, 128..254 in desc, 0 in neither.  Col ids are binned cyclically into
+ *              1..255 (col_split.hip: bin_id), so a wrap-around step still counts as ascending.
+ *            Sums are taken modulo 2^32; on a query's output cov <= m, so nothing wraps.
+ *   slots    a read's counting seeds in computation order -- largest pos first, the order of the
+ *            binary containers; the first min(n_seeds, max_seeds) of them fill the read's max_seeds
+ *            slots of seed_pos (u32), seed_len (u32), seed_cid (u8): read k owns
+ *            [k * max_seeds, (k+1) * max_seeds).  Unused slots hold COLBWT_SEED_NONE, 0 and 0.
+ * On a query's output: with min_len == 1, cov + resets == m; n_seeds <= resets + 1; max_len equals
+ * the largest stored len when min_len == 1 (and max_seeds >= n_seeds).
+ *
+ * colbwt_seeds_reduce_device is the reduction alone, over device buffers a colbwt_query_device call
+ * filled (d_pml of pml_bytes 2 or 4, d_cid, d_read_off; any arrays of that shape do); it needs no
+ * index and runs on the current device, which must hold the buffers.  d_pml and d_summary 16-byte
+ * aligned, d_cid 8-byte, d_seed_pos / d_seed_len 4-byte; the three slot arrays may all be NULL when
+ * only summaries are wanted.  Fewer than 2^32-1 reads per call, reads up to 2^32-1 bases.
+ * Asynchronous on `hip_stream` unless `stats` is given (then kernel_ms is its time).  The output is
+ * deterministic: no atomics are involved.
+ * colbwt_seeds_batch: reads in host memory as colbwt_query_batch takes them; the query (u16 PML, or
+ * u32 when a read is longer than 65535) and the reduction run on the device and only summaries and
+ * slots come back (seed_pos / seed_len / seed_cid all NULL: summaries only).  Sharded over the
+ * replicas of a colbwt_index_open_devices handle.  kernel_ms covers query + reduction.
+ * colbwt_seeds_file: FASTA/FASTQ(.gz) in (the reader and batch pipeline of colbwt_count_file), one
+ * line per read "name\tm\tn_seeds\tcov\tmax_len\tresets\tn_col\tcol_cov\tasc\tdesc\tpos:len:id,..\n"
+ * (the stored seeds; the last field is empty when there are none); out_path NULL => pattern + ".seeds". */
+#define COLBWT_SEED_NONE 0xFFFFFFFFu
+typedef struct colbwt_seed_summary {
+    uint32_t n_seeds, max_len, cov, resets, n_col, col_cov, asc, desc;
+} colbwt_seed_summary;
+int colbwt_seeds_reduce_device(const void *d_pml, int pml_bytes, const uint8_t *d_cid, const uint64_t *d_read_off, uint64_t n_reads,
+                               uint64_t n_bases, uint32_t min_len, uint32_t max_seeds, colbwt_seed_summary *d_summary,
+                               uint32_t *d_seed_pos, uint32_t *d_seed_len, uint8_t *d_seed_cid, void *hip_stream,
+                               colbwt_stats *stats);
+int colbwt_seeds_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t min_len,
+                       uint32_t max_seeds, colbwt_seed_summary *summary, uint32_t *seed_pos, uint32_t *seed_len, uint8_t *seed_cid,
+                       colbwt_stats *stats);
+int colbwt_seeds_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t min_len, uint32_t max_seeds,
+                      uint64_t batch_bases, colbwt_stats *stats);
+
 /* ---- index construction (SURVEY.md 8(f) "next" #1) ------------------------ */
 
 /* build_col_bwt <prefix> (src/build_col_bwt.cpp:14-52): reads <prefix>.bwt.heads,
