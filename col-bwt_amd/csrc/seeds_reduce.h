@@ -29,9 +29,14 @@
 // Lane 0's state after the tile goes to all lanes through LDS (wave-uniform: the read that crosses
 // into the next tile), so a read may be as long as the API allows; it is then one wave's work.
 // Unused slots are what the launch's three memsets left.
+//
+// The chunk is seeds_chunk(n_bases), 2048..16384 by batch size.  COLBWT_SEEDS_CHUNK=<bases>, read at
+// every launch like COLBWT_LINE_ROWS_CHUNK (fat_cursor.h), replaces it with a multiple of 512 in
+// 512..16384; 512..1536 is below anything production picks and exists so that small inputs have many waves.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "lane_io.h"
 
@@ -343,6 +348,13 @@ __global__ __launch_bounds__(kSeedsBlock) void seeds_reduce_kernel(const PmlT *_
 
 // bases per wave: long enough to amortise the wave's two searches, short enough that a batch fills the chip
 inline uint64_t seeds_chunk(uint64_t n_bases) {
+    // "<bases>": the tests' way to every chunk size, and to many waves, at batch sizes they can compare in
+    // full (tests/emu/seeds_emu.py depends on it); anything but a multiple of 512 in 512..16384 is ignored
+    if (const char *e = getenv("COLBWT_SEEDS_CHUNK")) {
+        char *end = nullptr;
+        const unsigned long long v = strtoull(e, &end, 10);
+        if (*e >= '0' && *e <= '9' && *end == 0 && v >= kSeedsTile && v <= 16384 && v % kSeedsTile == 0) return v;
+    }
     const uint64_t per = (n_bases / 65536 + kSeedsTile - 1) / kSeedsTile * kSeedsTile;
     return per < 2048 ? 2048 : per > 16384 ? 16384 : per;
 }

@@ -142,6 +142,145 @@ def check_crafted():
     print("ok crafted arrays through seeds_reduce_device")
 
 
+KNOB = helpers.SEEDS_KNOB
+WAVE_CHUNKS = (512, 1024, 2048, 2560, 16384)
+
+
+class knob:
+    """COLBWT_SEEDS_CHUNK=`chunk` for the launches inside (the library reads it at every launch)."""
+
+    def __init__(self, chunk):
+        self.chunk = chunk
+
+    def __enter__(self):
+        os.environ[KNOB] = str(self.chunk)
+
+    def __exit__(self, *exc):
+        del os.environ[KNOB]
+
+
+def lens_from_cuts(cuts, n_bases):
+    """Read lengths of a batch of n_bases bases cut at the positions `cuts`, in any order (a position
+    given n times: n - 1 empty reads there; 0 and n_bases are cuts already, so n times means n)."""
+    cuts = sorted([0] + [int(v) for v in cuts])
+    return np.diff(np.asarray(cuts + [n_bases], np.int64))
+
+
+def check_wave_boundaries():
+    """Which wave owns a read (csrc/seeds_reduce.h: the one whose chunk [w c, (w+1) c) holds the read's
+    first base; the last wave to the end), with the chunk c forced to 512, 1024, 2048, 2560 and 16384:
+    read starts and runs of empty reads placed on, one before and one after k c, a read over several
+    whole chunks, batches of exactly k c bases with and without trailing empty reads.  Every read of
+    every batch against the restatement, u16 and u32, with the slot arrays and without."""
+    rng = np.random.default_rng(23)
+    runs = {"launches": 0, "bases": 0}
+
+    def arrays(nb, dt, nonzero=(), zero=()):
+        """Random pml (about 15 % zeros) and col ids (about 20 % non-zero); `nonzero` / `zero`: ranges forced."""
+        pml = np.where(rng.random(nb) < 0.15, 0, rng.integers(1, 60, nb)).astype(dt)
+        if dt is np.uint32:
+            big = rng.random(nb) < 0.3
+            pml[big & (pml > 0)] += np.uint32(1 << 31)
+        for lo, hi in nonzero:
+            pml[max(lo, 0):min(hi, nb)] = 7
+        for lo, hi in zero:
+            pml[max(lo, 0):min(hi, nb)] = 0
+        cid = np.where(rng.random(nb) < 0.2, rng.integers(1, 256, nb), 0).astype(np.uint8)
+        return pml, cid
+
+    def run(label, c, lens, nonzero=(), zero=(), waves=None):
+        lens = np.asarray(lens, np.int64)
+        off = np.concatenate(([0], np.cumsum(lens))).astype(np.uint64)
+        nb = int(off[-1])
+        assert helpers.seeds_chunk(nb, os.environ) == c, (label, c)
+        if waves is not None:
+            assert helpers.seeds_waves(nb, c) == waves, (label, nb, c, waves)
+        for dt, params in ((np.uint16, ((1, 4), (3, 2))), (np.uint32, ((1, 3), (1 << 31, 5)))):
+            pml, cid = arrays(nb, dt, nonzero, zero)
+            for k, (min_len, max_seeds) in enumerate(params):
+                want = sr.seeds(pml, cid, off, min_len, max_seeds)
+                name = f"chunk {c}: {label}/{np.dtype(dt).name}/l{min_len}/k{max_seeds}"
+                same(name, reduce_device(pml, cid, off, min_len, max_seeds), want)
+                if k == 0:
+                    got = reduce_device(pml, cid, off, min_len, max_seeds, slots=False)
+                    assert np.array_equal(got[0], want[0]), f"{name}: summaries only"
+                    runs["launches"] += 1
+                runs["launches"] += 1
+                runs["bases"] += nb
+        return off
+
+    def fill(lo, hi, top):
+        """Read starts strictly inside (lo, hi), reads of up to about `top` bases."""
+        n = max((hi - lo) // max(top // 2, 1), 1)
+        return np.unique(rng.integers(lo + 1, hi, n)).tolist() if hi - lo > 1 else []
+
+    for c in WAVE_CHUNKS:
+        top = 300 if c < 16384 else 2500
+        with knob(c):
+            # read starts at c - 1 (the read, and a PML run inside it, span the boundary), 2c, 3c + 1 (base 3c
+            # is the last of the previous read and of its run), and one-base reads at 4c - 1, 4c, 4c + 1
+            cuts = [c - 1, 2 * c, 3 * c + 1, 4 * c - 1, 4 * c, 4 * c + 1]
+            for a, b in ((0, c - 1), (c + 40, 2 * c), (2 * c, 3 * c - 40), (3 * c + 1, 4 * c - 1), (4 * c + 2, 4 * c + 90)):
+                cuts += fill(a, b, top)
+            off = run("read starts", c, lens_from_cuts(cuts, 4 * c + 90), waves=5,
+                      nonzero=((c - 4, c + 5), (3 * c - 3, 3 * c + 1), (2 * c - 2, 2 * c + 3)), zero=((3 * c + 1, 3 * c + 2),))
+            for want_start in (c - 1, 2 * c, 3 * c + 1, 4 * c - 1, 4 * c, 4 * c + 1):
+                assert want_start in off
+            assert not ((off > c - 1) & (off <= c + 5)).any()
+            # runs of empty reads exactly at k c: at 0 (before the first read: nothing ends there), at c (after a
+            # read that ends there and before one that starts there), at 2c = n_bases (after the last read:
+            # nothing starts there).  More than 64 boundaries: the mark loop's second round.
+            for n_e in (1, 63, 64, 65, 200):
+                cuts = [0] * n_e + [c] * (n_e + 1) + [2 * c] * n_e + fill(0, c, top) + fill(c, 2 * c, top)
+                run(f"{n_e} empty reads at 0, c, 2c", c, lens_from_cuts(cuts, 2 * c), waves=2)
+            # the same run one base off the boundary on either side: the other wave owns it
+            cuts = [c - 1] * 66 + [2 * c + 1] * 66 + fill(0, c - 1, top) + fill(c, 2 * c, top) + fill(2 * c + 2, 2 * c + 60, top)
+            run("65 empty reads at c - 1 and 2c + 1", c, lens_from_cuts(cuts, 2 * c + 60), waves=3)
+            # one read of 3c + 17 bases from c - 5: the waves of [c, 4c) own nothing; tiny reads on both sides
+            tiny = rng.integers(0, 6, 4 * c)
+            left = tiny[:np.searchsorted(np.cumsum(tiny), c - 5, side="right")]
+            left = np.concatenate((left, [c - 5 - left.sum()]))
+            right = tiny[2 * c:2 * c + 150]
+            lens = np.concatenate((left, [3 * c + 17], right))
+            off = run("read over three whole chunks", c, lens, nonzero=((2 * c - 9, 2 * c + 9),), zero=((3 * c, 3 * c + 1),))
+            assert int(off[len(left)]) == c - 5 and int(off[len(left) + 1]) == 4 * c + 12
+            assert not ((off >= c) & (off < 4 * c)).any() and int(off[-1]) > 4 * c + 12
+            # n_bases an exact multiple of c
+            body = fill(0, 3 * c, top) + [c, 2 * c - 1]
+            run("n_bases 3c, the last read ends there", c, lens_from_cuts(body, 3 * c), waves=3)
+            for n_e in (1, 64, 70):
+                run(f"n_bases 2c and {n_e} trailing empty reads", c, lens_from_cuts(fill(0, 2 * c, top) + [2 * c] * n_e, 2 * c), waves=2)
+            for n_e in (3, 70):
+                cuts = [v for v in fill(0, c, top)] + [c - 7] + [2 * c] * n_e      # the last non-empty read: [c - 7, 2c)
+                cuts = [v for v in cuts if v <= c - 7 or v == 2 * c]
+                run(f"a read over the whole last chunk and {n_e} trailing empty reads", c, lens_from_cuts(cuts, 2 * c), waves=2)
+            run("n_bases c in one read", c, [c], waves=1)
+            run("n_bases c in one read, empty reads around", c, [0, 0, c, 0], waves=1)
+            if c == 16384:
+                # one wave, 32 tiles, about 6000 read ends (more than 64 in most tiles), one read of 600 bases
+                tiny = rng.integers(0, 6, 8000)
+                half = tiny[:np.searchsorted(np.cumsum(tiny), (c - 600) // 2)]
+                rest = tiny[4000:4000 + np.searchsorted(np.cumsum(tiny[4000:]), c - 600 - half.sum(), side="right")]
+                lens = np.concatenate((half, [600], rest, [c - 600 - half.sum() - rest.sum()]))
+                off = run("one wave of reads of 0..5 bases", c, lens, waves=1)
+                assert len(lens) > 5500 and int(off[-1]) == c
+                ends = np.bincount((off[1:][lens > 0] - 1).astype(np.int64) // 512, minlength=32)
+                assert (ends > 64).sum() >= 20, ends
+        print(f"ok wave boundaries at chunk {c}")
+    assert KNOB not in os.environ
+    print(f"ok wave boundaries: {runs['launches']} launches, {runs['bases']} bases compared")
+
+
+def check_batch_under_knob(image, reads):
+    """seeds_batch (the query, then the pass over the shard's rebased read_off) with the chunk forced
+    to 512 (many waves per shard) and to 16384 (one), one replica and two."""
+    for c in (512, 16384):
+        with knob(c):
+            assert helpers.seeds_chunk(int(sum(len(r) for r in reads)), os.environ) == c
+            check_index(image, reads, f"seeds_batch at chunk {c}", layouts=(2, LINE_ROWS_4), params=((1, 1000), (8, 3)))
+            check_replicas(image, reads)
+
+
 def check_file(image, reads):
     """colbwt_seeds_file on FASTA, FASTQ and .gz == a Python formatting of the restatement."""
     image = bytes(image)
@@ -233,6 +372,9 @@ def main():
     check_file(img, reads[:40] + [np.zeros(0, np.uint8)])
     check_replicas(img, reads)
     check_errors(img)
+    assert helpers.SEEDS_KNOB not in os.environ       # everything above ran with the product's own chunk
+    check_wave_boundaries()
+    check_batch_under_knob(img, reads)
     print("SEEDS-EMU-OK")
 
 

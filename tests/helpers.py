@@ -421,3 +421,27 @@ def chunk_plans(n_reads, resident, big, tail_permille):
         at += p.n
     assert at == n_reads
     return plans
+
+
+# ---- the seeds pass's wave chunk (csrc/seeds_reduce.h seeds_chunk), restated so that a test can
+# place reads relative to the wave boundaries k * chunk and assert which chunk its batch gets
+SEEDS_TILE = 512                     # kSeedsTile
+SEEDS_KNOB = "COLBWT_SEEDS_CHUNK"
+
+
+def seeds_chunk(n_bases, env=None):
+    """Bases per wave of a seeds launch over n_bases bases: ceil(n_bases / 65536 / 512) * 512 clamped to
+    2048..16384, unless COLBWT_SEEDS_CHUNK (looked up in the mapping `env`; None: no knob is set) holds
+    a multiple of 512 in 512..16384."""
+    text = (env or {}).get(SEEDS_KNOB)
+    if text is not None and text.isascii() and text.isdigit():
+        v = int(text)
+        if SEEDS_TILE <= v <= 16384 and v % SEEDS_TILE == 0:
+            return v
+    per = -(-(n_bases // 65536) // SEEDS_TILE) * SEEDS_TILE
+    return min(max(per, 2048), 16384)
+
+
+def seeds_waves(n_bases, chunk):
+    """Waves of the launch (launch_seeds_reduce): one per chunk of the bases, at least one."""
+    return -(-n_bases // chunk) if n_bases else 1

@@ -19,8 +19,8 @@ def seeds(pml, cid, read_off, min_len, max_seeds):
     sc = np.zeros((n_reads, max_seeds), np.uint8)
     for r in range(n_reads):
         lo, hi = int(read_off[r]), int(read_off[r + 1])
-        p = [int(v) for v in pml[lo:hi]]
-        c = [int(v) for v in cid[lo:hi]]
+        p = np.asarray(pml[lo:hi]).tolist()         # Python ints
+        c = np.asarray(cid[lo:hi]).tolist()
         m = hi - lo
         found = []                                  # every seed of the read, smallest pos first
         k = 0

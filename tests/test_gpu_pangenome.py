@@ -24,6 +24,7 @@ import pytest
 
 import helpers
 import sa_reference as sr
+import seeds_restatement as seeds_rs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -251,3 +252,31 @@ def test_pml_every_layout(pkg, oracle, pan, image):
         tbl.close()
         assert np.array_equal(p, ep), (layout, np.flatnonzero(p != ep)[:5])
         assert np.array_equal(c, ec), (layout, np.flatnonzero(c != ec)[:5])
+
+
+def test_seeds_every_layout(pkg, oracle, pan, image):
+    """seeds_batch on the reads of test_pml_every_layout == the restatement applied to the oracle's PML
+    and col ids, in every layout.  The col ids of this index come from real multi-MUM chains, so the
+    chain fields (n_col, asc, desc) see ids no synthetic table gives them."""
+    reads = [r for r in pan["reads"] if len(r) and min(r) > 1][::2][:1000]
+    bases, off = helpers.concat_reads([np.frombuffer(r, np.uint8) for r in reads])
+    ep, ec = oracle.OracleIndex(image).query_batch(bases, off)
+    params = ((1, 1000), (20, 8), (16, 16))
+    wants = {p: seeds_rs.seeds(ep, ec, off, *p) for p in params}
+    for p in params:
+        seeds_rs.check_invariants(*wants[p][:3], off, *p)
+    for field, name in ((4, "n_col"), (6, "asc"), (7, "desc")):
+        assert any((wants[p][0][:, field] > 0).any() for p in params), f"{name} > 0 occurs in the sample"
+    s = wants[(16, 16)][0]
+    print(f"\nseeds (16, 16): reads with n_col > 0 {int((s[:, 4] > 0).sum())}, asc > 0 {int((s[:, 6] > 0).sum())}, "
+          f"desc > 0 {int((s[:, 7] > 0).sum())} of {len(reads)}")
+    for layout in LAYOUTS:
+        tbl = pkg.ColPml.from_bytes(image, layout=layout)
+        for p in params:
+            summary, pos, ln, sc, st = tbl.seeds_batch(bases, off, *p)
+            assert st.n_reads == len(reads) and st.n_bases == int(off[-1])
+            for name, g, w in zip(("summary", "seed_pos", "seed_len", "seed_cid"), (summary.view(np.uint32).reshape(-1, 8), pos, ln, sc),
+                                  wants[p]):
+                bad = np.argwhere(g != w)
+                assert bad.size == 0, (layout, p, name, bad[:5].tolist(), g[tuple(bad[0])], w[tuple(bad[0])])
+        tbl.close()

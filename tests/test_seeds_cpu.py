@@ -93,14 +93,33 @@ def test_exports_and_header_declare_seeds():
         assert name in pkg.EXPORTS and name + "(" in header
 
 
+def test_seeds_chunk_restatement_is_pinned():
+    """helpers.seeds_chunk, the tests' restatement of seeds_chunk() in csrc/seeds_reduce.h, at values
+    derived by hand from ceil(n_bases / 65536 / 512) * 512 clamped to 2048..16384, and the knob's
+    rule: a multiple of 512 in 512..16384, anything else ignored."""
+    for n_bases, chunk in ((0, 2048), (18_000_000, 2048), (90_000_000, 2048), (134_283_263, 2048), (134_283_264, 2560),
+                           (140_000_000, 2560), (180_000_000, 3072), (400_000_000, 6144), (15873 * 65536 - 1, 15872),
+                           (15873 * 65536, 16384), (1_100_000_000, 16384), (1_500_000_000, 16384), (4_400_000_000, 16384)):
+        assert helpers.seeds_chunk(n_bases) == chunk, n_bases
+        assert helpers.seeds_chunk(n_bases, {}) == chunk and helpers.seeds_chunk(n_bases, {"OTHER": "512"}) == chunk
+    for text in ("512", "1024", "1536", "2048", "2560", "16384"):
+        assert helpers.seeds_chunk(400_000_000, {helpers.SEEDS_KNOB: text}) == int(text)
+    for text in ("", "0", "256", "513", "2049", "16896", "32768", "-512", "+512", " 512", "512 ", "0x200", "5e2", "2048,1"):
+        assert helpers.seeds_chunk(400_000_000, {helpers.SEEDS_KNOB: text}) == 6144, text
+    assert [helpers.seeds_waves(n, 2048) for n in (0, 1, 2048, 2049, 4096)] == [1, 1, 1, 2, 2]
+
+
 def test_emulated_seeds_kernel_matches_restatement_under_asan():
     """Layouts 1-3 and line rows, empty / 1-base / ragged / long reads, the u32 path, crafted arrays
     and alignment sweeps through seeds_reduce_device, seeds_file on FASTA / FASTQ / .gz, two
-    replicas -- kernel and host code under ASan."""
+    replicas; then read starts, runs of empty reads, a read over several chunks and batches of exactly
+    k chunks at the wave boundaries of COLBWT_SEEDS_CHUNK = 512, 1024, 2048, 2560 and 16384, and
+    seeds_batch with one and two replicas at 512 and 16384 -- kernel and host code under ASan."""
     emu = os.path.join(HERE, "emu")
     subprocess.check_call(["make", "-C", emu, "libcolbwt_emu.so"], stdout=subprocess.DEVNULL)
     asan = subprocess.check_output(["gcc", "-print-file-name=libasan.so"]).decode().strip()
     env = dict(os.environ, LD_PRELOAD=asan, ASAN_OPTIONS="detect_leaks=0")
+    env.pop(helpers.SEEDS_KNOB, None)
     out = subprocess.run([sys.executable, os.path.join(emu, "seeds_emu.py")], env=env,
                          capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0 and "SEEDS-EMU-OK" in out.stdout, out.stdout[-3000:] + out.stderr[-3000:]
