@@ -35,6 +35,7 @@ EXPORTS = (
     "colbwt_locate_device", "colbwt_locate_file",
     "colbwt_rlbwt_build_text_locate", "colbwt_rlbwt_build_files_locate", "colbwt_rlbwt_write_locate",
     "colbwt_seeds_reduce_device", "colbwt_seeds_batch", "colbwt_seeds_file",
+    "colbwt_docs_mask_words", "colbwt_docs_work_bytes", "colbwt_docs_batch", "colbwt_docs_device", "colbwt_docs_file",
 )
 
 SEED_NONE = 0xFFFFFFFF          # include/colbwt.h COLBWT_SEED_NONE: seed_pos of a slot past the read's min(n_seeds, max_seeds)
@@ -134,6 +135,13 @@ def lib():
     L.colbwt_seeds_reduce_device.argtypes = [vp, i32, vp, vp, u64, u64, u32, u32, vp, vp, vp, vp, vp, C.POINTER(Stats)]
     L.colbwt_seeds_batch.argtypes = [vp, vp, vp, u64, u32, u32, vp, vp, vp, vp, C.POINTER(Stats)]
     L.colbwt_seeds_file.argtypes = [vp, C.c_char_p, C.c_char_p, u32, u32, u64, C.POINTER(Stats)]
+    L.colbwt_docs_mask_words.argtypes = [vp]
+    L.colbwt_docs_mask_words.restype = u32
+    L.colbwt_docs_work_bytes.argtypes = [u64]
+    L.colbwt_docs_work_bytes.restype = u64
+    L.colbwt_docs_batch.argtypes = [vp, vp, vp, u64, u32, u32, vp, vp, vp, vp, vp, vp, C.POINTER(Stats)]
+    L.colbwt_docs_device.argtypes = [vp, vp, vp, u64, u64, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Stats)]
+    L.colbwt_docs_file.argtypes = [vp, C.c_char_p, C.c_char_p, u32, u32, u64, C.POINTER(Stats)]
     _lib = L
     return L
 
@@ -375,6 +383,58 @@ class ColPml:
                                         int(max_occ), batch_bases, C.byref(st)))
         return st
 
+    # -- docs: the documents holding each read's longest exact match (include/colbwt.h colbwt_docs_*) --
+    def docs_mask_words(self):
+        """W = ceil(n_docs / 64): u64 mask words per read (0 when no locate samples are attached)."""
+        return int(lib().colbwt_docs_mask_words(self._h))
+
+    def docs_batch(self, bases, read_off, min_len=16, max_walk=256, want_tally=True):
+        """Many reads -> (mlen uint32, occ uint64, n_hit uint32, mask uint64 [n_reads, W], doc_reads, doc_only, Stats):
+        bit d & 63 of mask[k, d >> 6] is set iff one of the first min(occ, max_walk) occurrences of read k's longest
+        matching suffix (of at least min_len bases) starts in document d; doc_reads[d] / doc_only[d] (uint64 [n_docs],
+        None each when not want_tally) count the reads hitting d / hitting d alone.  Everything runs on the device."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        n_reads = max(read_off.size - 1, 0)
+        words = self.docs_mask_words()
+        mlen = np.zeros(n_reads, np.uint32)
+        occ = np.zeros(n_reads, np.uint64)
+        n_hit = np.zeros(n_reads, np.uint32)
+        mask = np.zeros((n_reads, words), np.uint64)
+        n_docs = self.locate_docs().size if want_tally and words else 0
+        doc_reads = np.zeros(n_docs, np.uint64) if want_tally else None
+        doc_only = np.zeros(n_docs, np.uint64) if want_tally else None
+        st = Stats()
+        _check(lib().colbwt_docs_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n_reads, int(min_len), int(max_walk),
+                                       mlen.ctypes.data, occ.ctypes.data, n_hit.ctypes.data, mask.ctypes.data,
+                                       doc_reads.ctypes.data if want_tally else None, doc_only.ctypes.data if want_tally else None,
+                                       C.byref(st)))
+        return mlen, occ, n_hit, mask, doc_reads, doc_only, st
+
+    def docs(self, pattern, min_len=16, max_walk=256):
+        """One read -> (mlen, occ, [document numbers, ascending]) as ints."""
+        p = np.frombuffer(bytes(pattern), dtype=np.uint8)
+        mlen, occ, _, mask, _, _, _ = self.docs_batch(p, np.array([0, p.size], np.uint64), min_len, max_walk, want_tally=False)
+        return int(mlen[0]), int(occ[0]), _mask_docs(mask[0])
+
+    def docs_device(self, d_bases, d_read_off, n_reads, n_bases, min_len, max_walk, d_mlen, d_occ, d_n_hit, d_mask, d_work,
+                    d_doc_reads=None, d_doc_only=None, d_order=None, stream=0, timed=False):
+        """Device-resident docs entry point: raw device pointers (ints).  d_mask holds n_reads * docs_mask_words() u64,
+        d_work docs_work_bytes(n_reads) bytes (256-byte aligned); the tallies (n_docs u64 each, or None) are ADDED to."""
+        st = Stats()
+        _check(lib().colbwt_docs_device(self._h, d_bases, d_read_off, n_reads, n_bases, int(min_len), int(max_walk), d_mlen, d_occ,
+                                        d_n_hit, d_mask, d_doc_reads, d_doc_only, d_work, d_order, stream,
+                                        C.byref(st) if timed else None))
+        return st
+
+    def docs_file(self, pattern_path, out_path=None, min_len=16, max_walk=256, batch_bases=0):
+        """FASTA/FASTQ(.gz) -> text lines "name\tm\tmlen\tocc\tn_hit\td,d,.." (default <pattern>.docs) and
+        <out>.tally, one line "d\tdoc_reads\tdoc_only" per document."""
+        st = Stats()
+        _check(lib().colbwt_docs_file(self._h, os.fsencode(pattern_path), os.fsencode(out_path) if out_path else None,
+                                      int(min_len), int(max_walk), batch_bases, C.byref(st)))
+        return st
+
     def cid_dictionary(self):
         """The distinct col ids the table's rows hold, ascending (uint8 array): the dictionary of the gather codec."""
         ids = np.zeros(256, np.uint8)
@@ -405,6 +465,16 @@ def doc_offsets(positions, doc_start):
     doc_start = np.asarray(doc_start, np.uint64)
     doc = np.searchsorted(doc_start, positions, side="right").astype(np.int64) - 1
     return doc, positions - doc_start[doc]
+
+
+def docs_work_bytes(n_reads):
+    """colbwt_docs_work_bytes: size of the device workspace a docs_device call over n_reads reads needs."""
+    return int(lib().colbwt_docs_work_bytes(int(n_reads)))
+
+
+def _mask_docs(mask_row):
+    """One read's mask words (ColPml.docs_batch) -> its document numbers, ascending."""
+    return [64 * w + b for w, x in enumerate(np.asarray(mask_row, np.uint64).tolist()) for b in range(64) if (x >> b) & 1]
 
 
 def binary_to_text(bin_path, value_bytes, text_path):

@@ -23,6 +23,7 @@
 #include "../../include/colbwt.h"
 #include "bin_writer.h"
 #include "count_query.h"
+#include "docs_query.h"
 #include "fasta_parallel.h"
 #include "fastx_reader.h"
 #include "index.h"
@@ -111,16 +112,22 @@ constexpr int kFileBatches = 3;   // batches of reads in flight in colbwt_query_
 // layout in HBM that ends a folded run, the phi samples and their bucket directory.
 struct LocateTables {
     DevPtr toe_row, pair, dir;
+    DevPtr doc_dev;                     // doc_start as u32 in HBM: the walk of colbwt_docs_* looks positions up in it
     uint32_t shift = 0;
     uint64_t n_buckets = 0;
     std::vector<uint64_t> doc_start;    // host copy: positions -> (document, offset) in colbwt_locate_file
     bool ready() const { return toe_row.get() != nullptr; }
-    uint64_t bytes() const { return toe_row.bytes() + pair.bytes() + dir.bytes(); }
+    uint64_t bytes() const { return toe_row.bytes() + pair.bytes() + dir.bytes() + doc_dev.bytes(); }
+    uint32_t n_docs() const { return (uint32_t)doc_start.size(); }
+    DocsArgs docs(uint32_t min_len, uint32_t max_walk) const {
+        return DocsArgs{toe_row.as<const uint32_t>(), phi(), doc_dev.as<const uint32_t>(), n_docs(), min_len, max_walk};
+    }
     PhiTable phi() const { return PhiTable{pair.as<const uint2>(), dir.as<const uint32_t>(), shift, (uint32_t)(n_buckets - 1)}; }
     void reset() {
         toe_row.reset();
         pair.reset();
         dir.reset();
+        doc_dev.reset();
         doc_start.clear();
     }
 };
@@ -607,6 +614,81 @@ int locate_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *re
                          part);
 }
 
+const char *kDocsTooMany = "more than 4096 documents";   // kDocsLds: doc_start and the tally live in a block's LDS
+
+const char *docs_bad_params(uint32_t min_len, uint32_t max_walk) {
+    if (min_len == 0) return "min_len must be at least 1";
+    if (max_walk == 0 || max_walk > kDocsMaxWalk) return "max_walk must be 1 .. 2^20";
+    return nullptr;
+}
+
+// Docs (docs_query.h) for a batch in host memory: search, order, walk and tally run back to back on
+// the replica's stream; positions never leave HBM.  The first result array of the scratch holds mlen,
+// then n_hit; the second the workspace, occ, the masks and the shard's two tallies, which are summed
+// on the host (doc_reads / doc_only receive the totals of the call).
+int docs_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t min_len,
+                   uint32_t max_walk, uint32_t *mlen, uint64_t *occ, uint32_t *n_hit, uint64_t *mask, uint64_t *doc_reads,
+                   uint64_t *doc_only, colbwt_stats *stats) {
+    if (idx) {
+        if (const char *m = docs_bad_params(min_len, max_walk)) return fail(COLBWT_ERR_ARG, m);
+        if (!idx->loc.ready()) return fail(COLBWT_ERR_ARG, "no locate samples attached (colbwt_index_attach_locate)");
+        for (colbwt_index *r : idx->more)
+            if (!r->loc.ready()) return fail(COLBWT_ERR_ARG, "no locate samples attached (colbwt_index_attach_locate)");
+        if (idx->loc.n_docs() > kDocsLds) return fail(COLBWT_ERR_ARG, kDocsTooMany);
+        if (n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, "more than 2^32-2 reads in a batch");
+    }
+    const uint32_t n_docs = idx ? idx->loc.n_docs() : 0, n_words = docs_mask_words(n_docs);
+    const bool tally = doc_reads || doc_only;
+    std::vector<uint64_t> total(tally ? 2 * (size_t)n_docs : 0, 0);   // the caller's arrays are written on success only
+    std::mutex tally_mu;
+    auto bad_pointers = [&](uint64_t n_bases) -> const char * {
+        return (n_bases && !bases) || !mlen || !occ || !n_hit || !mask ? "null bases/mlen/occ/n_hit/mask" : nullptr;
+    };
+    auto part = [&](colbwt_index *rep, uint64_t lo, uint64_t hi, uint64_t max_len, uint64_t min_read, colbwt_stats *st,
+                    std::string &msg) {
+        const uint64_t n = hi - lo, off0 = read_off[lo];
+        const uint64_t work = docs_work_bytes(n), mask_bytes = n * n_words * sizeof(uint64_t);
+        const uint64_t out_bytes[2] = {2 * n * sizeof(uint32_t), work + n * sizeof(uint64_t) + mask_bytes + 16ull * n_docs};
+        std::vector<uint64_t> shard(tally ? 2 * (size_t)n_docs : 0);
+        hipError_t launched = hipSuccess;
+        auto launch = [&](const DeviceBatch &b) {
+            uint32_t *d_mlen = (uint32_t *)b.out[0];
+            uint64_t *d_occ = (uint64_t *)((uint8_t *)b.out[1] + work), *d_mask = d_occ + n, *d_tally = d_mask + n * n_words;
+            if (tally) launched = hipMemsetAsync(d_tally, 0, 16ull * n_docs, b.stream);
+            if (launched == hipSuccess)
+                launched = launch_docs(rep->ix, rep->loc.docs(min_len, max_walk), b.bases, b.off, n, d_mlen, d_occ, d_mlen + n, d_mask,
+                                       doc_reads ? d_tally : nullptr, doc_only ? d_tally + n_docs : nullptr, b.out[1], b.order,
+                                       b.stream);
+        };
+        auto fetch = [&](const DeviceBatch &b) {
+            TRY_HIP(launched, b.stream, msg);
+            const uint32_t *d_mlen = (const uint32_t *)b.out[0];
+            const uint64_t *d_occ = (const uint64_t *)((const uint8_t *)b.out[1] + work), *d_mask = d_occ + n;
+            TRY_HIP(hipMemcpyAsync(mlen + lo, d_mlen, n * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            TRY_HIP(hipMemcpyAsync(n_hit + lo, d_mlen + n, n * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            TRY_HIP(hipMemcpyAsync(occ + lo, d_occ, n * sizeof(uint64_t), hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            if (mask_bytes)
+                TRY_HIP(hipMemcpyAsync(mask + lo * n_words, d_mask, mask_bytes, hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            if (tally)
+                TRY_HIP(hipMemcpyAsync(shard.data(), d_mask + n * n_words, 16ull * n_docs, hipMemcpyDeviceToHost, b.stream), b.stream,
+                        msg);
+            return COLBWT_OK;
+        };
+        const int rc = replica_batch(rep, bases + off0, read_off + lo, off0, n, max_len, min_read, true, out_bytes, 0, st, msg, launch,
+                                     fetch);
+        if (rc == COLBWT_OK && tally) {
+            std::lock_guard<std::mutex> g(tally_mu);
+            for (size_t d = 0; d < total.size(); ++d) total[d] += shard[d];
+        }
+        return rc;
+    };
+    const int rc = sharded_batch(idx, read_off, n_reads, 0xFFFFFFFFull, "read longer than 2^32-1 bases", true, stats, bad_pointers,
+                                 part);
+    if (rc == COLBWT_OK && doc_reads) std::copy(total.begin(), total.begin() + n_docs, doc_reads);
+    if (rc == COLBWT_OK && doc_only) std::copy(total.begin() + n_docs, total.end(), doc_only);
+    return rc;
+}
+
 // Largest max_seeds: results are n_reads x max_seeds slots of 9 bytes, in host memory and in HBM.
 constexpr uint32_t kSeedsMaxSeeds = 1u << 16;
 
@@ -732,6 +814,8 @@ int attach_one(colbwt_index *rep, const LocFile &f, std::string &msg) {
     TRY_HIP(L.toe_row.alloc(4 * rows), nullptr, msg);
     TRY_HIP(L.pair.alloc(8 * f.s), nullptr, msg);
     TRY_HIP(L.dir.alloc(4 * (n_buckets + 1)), nullptr, msg);
+    TRY_HIP(L.doc_dev.alloc(4 * (uint64_t)f.n_docs), nullptr, msg);
+    TRY_HIP(hipMemcpy(L.doc_dev.get(), f.doc_start, 4 * (uint64_t)f.n_docs, hipMemcpyHostToDevice), nullptr, msg);
     TRY_HIP(hipMemcpy(end_sa.get(), f.end_sa, 4 * f.r, hipMemcpyHostToDevice), nullptr, msg);
     TRY_HIP(hipMemcpy(L.pair.get(), f.pair, 8 * f.s, hipMemcpyHostToDevice), nullptr, msg);
     TRY_HIP(hipMemset(L.toe_row.get(), 0, 4 * rows), nullptr, msg);
@@ -1046,11 +1130,16 @@ int colbwt_query_device_ordered(colbwt_index *idx, const uint8_t *d_bases, const
 // one line per read "name\tm\tmlen\tocc\n" in pml_name (cid_name unused).  `locate_k` > 0 (with
 // `count`): locate queries (locate_query.h) with max_occ = locate_k, the line followed by
 // "\tdoc:offset,doc:offset,..".  `seeds_k` > 0 (with `count`): seeds (seeds_reduce.h) with min_len =
-// seeds_min and max_seeds = seeds_k, one line per read as colbwt_seeds_file documents it.
+// seeds_min and max_seeds = seeds_k, one line per read as colbwt_seeds_file documents it.  `docs_w` > 0
+// (with `count`): docs (docs_query.h) with min_len = docs_min and max_walk = docs_w, one line per read
+// and, after the last batch, pml_name + ".tally", as colbwt_docs_file documents them.
 static int query_file_impl(colbwt_index *idx, const char *pattern_path, const std::string &pml_name,
                            const std::string &cid_name, uint64_t batch_bases, colbwt_stats *stats, bool binary,
-                           bool count = false, uint32_t locate_k = 0, uint32_t seeds_min = 0, uint32_t seeds_k = 0) {
+                           bool count = false, uint32_t locate_k = 0, uint32_t seeds_min = 0, uint32_t seeds_k = 0,
+                           uint32_t docs_min = 0, uint32_t docs_w = 0) {
     if (stats) memset(stats, 0, sizeof(*stats));
+    const uint32_t docs_n = docs_w ? idx->loc.n_docs() : 0, docs_words = docs_mask_words(docs_n);
+    std::vector<uint64_t> docs_tally(2 * (size_t)docs_n, 0), docs_part(2 * (size_t)docs_n, 0);   // doc_reads, then doc_only
     const size_t replicas = 1 + idx->more.size();
     if (batch_bases == 0) batch_bases = (64ull << 20) * replicas;
     ParallelFasta fasta;
@@ -1157,6 +1246,22 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
                 free_q.push(b);
                 continue;
             }
+            if (docs_w) {
+                const uint32_t *ml = b->pml->as<uint32_t>(), *nh = ml + n_reads;
+                const uint64_t *oc = b->cid->as<uint64_t>(), *mk = oc + n_reads;   // docs_words mask words per read
+                for (uint64_t k = 0; k < n_reads && count_ok; ++k) {
+                    count_ok = fprintf(wn, "%s\t%llu\t%u\t%llu\t%u\t", b->names[k].c_str(),
+                                       (unsigned long long)(b->off[k + 1] - b->off[k]), ml[k], (unsigned long long)oc[k], nh[k]) > 0;
+                    bool first = true;
+                    for (uint32_t wi = 0; wi < docs_words && count_ok; ++wi)
+                        for (uint64_t m = mk[k * docs_words + wi]; m && count_ok; m &= m - 1, first = false)
+                            count_ok = fprintf(wn, first ? "%u" : ",%u", wi * 64u + (uint32_t)__builtin_ctzll(m)) > 0;
+                    count_ok = count_ok && fputc('\n', wn) != EOF;
+                }
+                t_format += now() - t0;
+                free_q.push(b);
+                continue;
+            }
             if (count) {
                 const uint32_t *ml = b->pml->as<uint32_t>();
                 const uint64_t *oc = b->cid->as<uint64_t>();
@@ -1212,7 +1317,9 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
         rc = select_device(idx->ix.device(), g_err);
         if (rc == COLBWT_OK && seeds_k && (!b->pml->ensure(n_reads * 32) || !b->cid->ensure(n_reads * 9 * (uint64_t)seeds_k)))
             rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
-        if (rc == COLBWT_OK && count && !seeds_k && (!b->pml->ensure(n_reads * 4) || !b->cid->ensure(n_reads * 8 * (1 + (uint64_t)locate_k))))
+        if (rc == COLBWT_OK && docs_w && (!b->pml->ensure(n_reads * 8) || !b->cid->ensure(n_reads * 8 * (1 + (uint64_t)docs_words))))
+            rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
+        if (rc == COLBWT_OK && count && !seeds_k && !docs_w && (!b->pml->ensure(n_reads * 4) || !b->cid->ensure(n_reads * 8 * (1 + (uint64_t)locate_k))))
             rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
         if (rc == COLBWT_OK && !count && (!b->cid->ensure(nb) || !b->pml->ensure(nb * (b->wide ? 4 : 2))))
             rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
@@ -1221,6 +1328,11 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
             uint32_t *sp = b->cid->as<uint32_t>(), *sl = sp + n_reads * seeds_k;
             rc = seeds_batch_all(idx, b->bases.data(), b->off.data(), n_reads, seeds_min, seeds_k, b->pml->as<uint32_t>(), sp, sl,
                                  (uint8_t *)(sl + n_reads * seeds_k), &st);
+        } else if (docs_w) {
+            rc = docs_batch_all(idx, b->bases.data(), b->off.data(), n_reads, docs_min, docs_w, b->pml->as<uint32_t>(),
+                                b->cid->as<uint64_t>(), b->pml->as<uint32_t>() + n_reads, b->cid->as<uint64_t>() + n_reads,
+                                docs_part.data(), docs_part.data() + docs_n, &st);
+            for (size_t d = 0; rc == COLBWT_OK && d < docs_tally.size(); ++d) docs_tally[d] += docs_part[d];
         } else if (locate_k) {
             rc = locate_batch_all(idx, b->bases.data(), b->off.data(), n_reads, locate_k, b->pml->as<uint32_t>(), b->cid->as<uint64_t>(),
                                   b->cid->as<uint64_t>() + n_reads, &st);
@@ -1261,6 +1373,15 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
     if (rc != COLBWT_OK) return rc;     // message set by the failing call on this thread
     if (reader_failed.load()) return fail(COLBWT_ERR_IO, std::string("cannot re-open pattern file ") + pattern_path);
     if (!okp || !okc) return fail(COLBWT_ERR_IO, "short write on " + pml_name + " / " + cid_name);
+    if (docs_w) {
+        const std::string tally_name = pml_name + ".tally";
+        FILE *wt = fopen(tally_name.c_str(), "wb");
+        if (!wt) return fail(COLBWT_ERR_IO, "cannot create " + tally_name);
+        bool ok = true;
+        for (uint32_t d = 0; d < docs_n && ok; ++d)
+            ok = fprintf(wt, "%u\t%llu\t%llu\n", d, (unsigned long long)docs_tally[d], (unsigned long long)docs_tally[docs_n + d]) > 0;
+        if (fclose(wt) != 0 || !ok) return fail(COLBWT_ERR_IO, "short write on " + tally_name);
+    }
     return COLBWT_OK;
 }
 
@@ -1456,6 +1577,63 @@ int colbwt_locate_file(colbwt_index *idx, const char *pattern_path, const char *
     if (batch_bases == 0)   // the default batch of the file query, cut so that max_occ slots per read stay ~tens of MB
         batch_bases = std::max<uint64_t>(1ull << 20, (64ull << 20) * (1 + idx->more.size()) * 16 / std::max<uint32_t>(16, max_occ));
     return query_file_impl(idx, pattern_path, out, out, batch_bases, stats, false, true, max_occ);
+}
+
+uint32_t colbwt_docs_mask_words(const colbwt_index *idx) {
+    return idx && idx->loc.ready() ? docs_mask_words(idx->loc.n_docs()) : 0;
+}
+
+uint64_t colbwt_docs_work_bytes(uint64_t n_reads) { return docs_work_bytes(n_reads); }
+
+int colbwt_docs_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t min_len,
+                      uint32_t max_walk, uint32_t *mlen, uint64_t *occ, uint32_t *n_hit, uint64_t *mask, uint64_t *doc_reads,
+                      uint64_t *doc_only, colbwt_stats *stats) {
+    return docs_batch_all(idx, bases, read_off, n_reads, min_len, max_walk, mlen, occ, n_hit, mask, doc_reads, doc_only, stats);
+}
+
+int colbwt_docs_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads, uint64_t n_bases,
+                       uint32_t min_len, uint32_t max_walk, uint32_t *d_mlen, uint64_t *d_occ, uint32_t *d_n_hit, uint64_t *d_mask,
+                       uint64_t *d_doc_reads, uint64_t *d_doc_only, void *d_work, const uint32_t *d_order, void *hip_stream,
+                       colbwt_stats *stats) {
+    auto bad_argument = [&]() -> const char * {
+        if (const char *m = docs_bad_params(min_len, max_walk)) return m;
+        if (!idx->loc.ready()) return "no locate samples attached (colbwt_index_attach_locate)";
+        for (colbwt_index *r : idx->more)
+            if (!r->loc.ready()) return "no locate samples attached (colbwt_index_attach_locate)";
+        if (idx->loc.n_docs() > kDocsLds) return kDocsTooMany;
+        if (n_reads == 0) return nullptr;
+        if (!d_bases || !d_read_off || !d_mlen || !d_occ) return "null device pointer";
+        if (((uintptr_t)d_bases & 15) || ((uintptr_t)d_mlen & 3) || ((uintptr_t)d_occ & 7))
+            return "d_bases must be 16-byte aligned, d_mlen 4-byte and d_occ 8-byte aligned";
+        if (n_reads >= 0xFFFFFFFFull) return "more than 2^32-2 reads in a batch";
+        if (!d_n_hit || !d_mask || !d_work) return "null d_n_hit/d_mask/d_work";
+        if (((uintptr_t)d_n_hit & 3) || ((uintptr_t)d_mask & 7) || ((uintptr_t)d_doc_reads & 7) || ((uintptr_t)d_doc_only & 7))
+            return "d_n_hit must be 4-byte aligned, d_mask/d_doc_reads/d_doc_only 8-byte aligned";
+        if ((uintptr_t)d_work & 255) return "d_work must be 256-byte aligned";
+        return nullptr;
+    };
+    hipError_t launched = hipSuccess;
+    const int rc = device_entry(idx, d_bases, n_reads, n_bases, hip_stream, 0, stats, bad_argument,
+                                [&](const Index &ix, hipStream_t stream) {
+                                    const LocateTables &L = replica_for(idx, d_bases)->loc;
+                                    launched = launch_docs(ix, L.docs(min_len, max_walk), d_bases, d_read_off, n_reads, d_mlen, d_occ,
+                                                           d_n_hit, d_mask, d_doc_reads, d_doc_only, d_work, d_order, stream);
+                                });
+    if (rc == COLBWT_OK && launched != hipSuccess) return hip_failed(launched, "colbwt_docs_device", nullptr, g_err);
+    return rc;
+}
+
+int colbwt_docs_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t min_len, uint32_t max_walk,
+                     uint64_t batch_bases, colbwt_stats *stats) {
+    if (!idx || !pattern_path) return fail(COLBWT_ERR_ARG, "null argument");
+    if (const char *m = docs_bad_params(min_len, max_walk)) return fail(COLBWT_ERR_ARG, m);
+    if (!idx->loc.ready()) return fail(COLBWT_ERR_ARG, "no locate samples attached (colbwt_index_attach_locate)");
+    if (idx->loc.n_docs() > kDocsLds) return fail(COLBWT_ERR_ARG, kDocsTooMany);
+    const std::string out = out_path ? out_path : std::string(pattern_path) + ".docs";
+    if (batch_bases == 0)   // the default batch of the file query, cut so that W mask words per read stay ~tens of MB
+        batch_bases = std::max<uint64_t>(1ull << 20, (64ull << 20) * (1 + idx->more.size()) * 16 /
+                                                         std::max<uint32_t>(16, docs_mask_words(idx->loc.n_docs())));
+    return query_file_impl(idx, pattern_path, out, out, batch_bases, stats, false, true, 0, 0, 0, min_len, max_walk);
 }
 
 int colbwt_binary_to_text(const char *bin_path, int value_bytes, const char *text_path) {

@@ -337,6 +337,53 @@ int colbwt_seeds_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *
 int colbwt_seeds_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t min_len, uint32_t max_seeds,
                       uint64_t batch_bases, colbwt_stats *stats);
 
+/* ---- docs: the documents holding each read's longest exact match ---------------------------
+ * "Which genomes contain this read?", answered on the device: locate's search, then a walk over the
+ * occurrences that keeps only the DOCUMENT of each, so that a bit mask per read and a tally per batch
+ * leave the device instead of max_occ positions per read.  The reference has no such mode; these
+ * semantics are this project's own.  Parameters min_len >= 1 and max_walk in 1 .. 2^20; locate samples
+ * must be attached (colbwt_index_attach_locate); n_docs and doc_start are the attached .col_loc's
+ * (colbwt_locate_docs), at most 4096 documents (more are an argument error of the three entry
+ * points, checked right after the samples), W = ceil(n_docs / 64) = colbwt_docs_mask_words (0 when no samples are attached).
+ *   search   exactly colbwt_locate_*'s: a read byte <= 1 ends it.  mlen and occ are as locate defines
+ *            them and are reported for every read, whatever min_len is.
+ *   walked   w = min(occ, max_walk) when mlen >= min_len, otherwise w = 0.  The walked positions are
+ *            locate's first w: SA[ep], SA[ep-1], .., SA[ep-w+1].
+ *   mask     read k owns the u64 words [k * W, (k+1) * W).  Bit d & 63 of word d >> 6 is set iff a walked
+ *            position p has doc_start[d] <= p and (d == n_docs-1 or p < doc_start[d+1]): an occurrence
+ *            belongs to the document its first character lies in.  Bits at or above n_docs are 0.
+ *   n_hit    (u32) the number of set bits.  A read's set is complete iff occ <= max_walk or
+ *            n_hit == n_docs (the walk may stop once n_hit == n_docs: that cannot change an output).
+ *   tally    doc_reads[d] counts the reads whose mask has bit d, doc_only[d] the reads with n_hit == 1
+ *            and bit d (both nullable, u64[n_docs]).  The device entry point ADDS to what the arrays
+ *            hold, so a caller accumulates over batches; the host entry point writes the totals of its
+ *            call.  Integer adds: the result does not depend on their order.
+ *
+ * Arguments, error codes, sharding over replicas, stream and stats as colbwt_locate_batch / _device /
+ * _file ("no locate samples attached" is an argument error); kernel_ms covers every stage (search,
+ * order, walk, tally).  Device form: allocates nothing; d_work must be 256-byte aligned and hold
+ * colbwt_docs_work_bytes(n_reads) bytes, and calls in flight at once need distinct work buffers.
+ * d_mask and the tallies 8-byte aligned, d_n_hit 4-byte; fewer than 2^32-1 reads per call; d_order
+ * (nullable) is advisory and goes to the search stage only -- the walk runs over the reads sorted by w.
+ * The host form takes its scratch as colbwt_locate_batch does and sums the shards' tallies on the host.
+ * colbwt_docs_file: FASTA/FASTQ(.gz) in (the reader and batch pipeline of colbwt_locate_file), one
+ * line per read "name\tm\tmlen\tocc\tn_hit\td,d,..\n" (document numbers ascending; the last field is
+ * empty when n_hit == 0), out_path NULL => pattern + ".docs"; after the last batch <out>.tally, one
+ * line "d\tdoc_reads\tdoc_only\n" per document; batch_bases 0 is colbwt_query_file's default, cut by
+ * W / 16 when W > 16 as colbwt_locate_file cuts it by max_occ.  A failing colbwt_docs_batch leaves
+ * doc_reads / doc_only as they were. */
+uint32_t colbwt_docs_mask_words(const colbwt_index *idx);
+uint64_t colbwt_docs_work_bytes(uint64_t n_reads);
+int colbwt_docs_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t min_len,
+                      uint32_t max_walk, uint32_t *mlen, uint64_t *occ, uint32_t *n_hit, uint64_t *mask, uint64_t *doc_reads,
+                      uint64_t *doc_only, colbwt_stats *stats);
+int colbwt_docs_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads, uint64_t n_bases,
+                       uint32_t min_len, uint32_t max_walk, uint32_t *d_mlen, uint64_t *d_occ, uint32_t *d_n_hit, uint64_t *d_mask,
+                       uint64_t *d_doc_reads, uint64_t *d_doc_only, void *d_work, const uint32_t *d_order, void *hip_stream,
+                       colbwt_stats *stats);
+int colbwt_docs_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t min_len, uint32_t max_walk,
+                     uint64_t batch_bases, colbwt_stats *stats);
+
 /* ---- index construction (SURVEY.md 8(f) "next" #1) ------------------------ */
 
 /* build_col_bwt <prefix> (src/build_col_bwt.cpp:14-52): reads <prefix>.bwt.heads,
