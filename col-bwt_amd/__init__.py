@@ -36,6 +36,8 @@ EXPORTS = (
     "colbwt_rlbwt_build_text_locate", "colbwt_rlbwt_build_files_locate", "colbwt_rlbwt_write_locate",
     "colbwt_seeds_reduce_device", "colbwt_seeds_batch", "colbwt_seeds_file",
     "colbwt_docs_mask_words", "colbwt_docs_work_bytes", "colbwt_docs_batch", "colbwt_docs_device", "colbwt_docs_file",
+    "colbwt_locate_all_tile", "colbwt_locate_all_work_bytes", "colbwt_locate_all_plan_device", "colbwt_locate_all_fill_device",
+    "colbwt_locate_all_batch", "colbwt_locate_all_file",
 )
 
 SEED_NONE = 0xFFFFFFFF          # include/colbwt.h COLBWT_SEED_NONE: seed_pos of a slot past the read's min(n_seeds, max_seeds)
@@ -142,6 +144,14 @@ def lib():
     L.colbwt_docs_batch.argtypes = [vp, vp, vp, u64, u32, u32, vp, vp, vp, vp, vp, vp, C.POINTER(Stats)]
     L.colbwt_docs_device.argtypes = [vp, vp, vp, u64, u64, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Stats)]
     L.colbwt_docs_file.argtypes = [vp, C.c_char_p, C.c_char_p, u32, u32, u64, C.POINTER(Stats)]
+    L.colbwt_locate_all_tile.argtypes = []
+    L.colbwt_locate_all_tile.restype = u32
+    L.colbwt_locate_all_work_bytes.argtypes = [u64]
+    L.colbwt_locate_all_work_bytes.restype = u64
+    L.colbwt_locate_all_plan_device.argtypes = [vp, vp, vp, u64, u64, u32, u64, vp, vp, vp, vp, vp, vp, C.POINTER(u64), C.POINTER(Stats)]
+    L.colbwt_locate_all_fill_device.argtypes = [vp, u64, u64, u64, vp, vp, u64, vp, vp, C.POINTER(Stats)]
+    L.colbwt_locate_all_batch.argtypes = [vp, vp, vp, u64, u32, u64, vp, vp, vp, vp, u64, C.POINTER(Stats)]
+    L.colbwt_locate_all_file.argtypes = [vp, C.c_char_p, C.c_char_p, u32, u64, u64, C.POINTER(Stats)]
     _lib = L
     return L
 
@@ -149,6 +159,12 @@ def lib():
 def _check(rc):
     if rc != 0:
         raise ColbwtError(rc, lib().colbwt_last_error().decode("utf-8", "replace"))
+
+
+def __getattr__(name):
+    if name == "LOCATE_ALL_TILE":   # colbwt_locate_all_tile: positions per tile of a locate-all walk, as the library was built
+        return int(lib().colbwt_locate_all_tile())
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def version():
@@ -383,6 +399,62 @@ class ColPml:
                                         int(max_occ), batch_bases, C.byref(st)))
         return st
 
+    # -- locate-all: every occurrence, as compressed sparse rows (include/colbwt.h colbwt_locate_all_*) --
+    def locate_all_batch(self, bases, read_off, min_len=16, max_per_read=0):
+        """Many reads -> (mlen uint32, occ uint64, pos_off uint64 [n_reads + 1], pos uint64 [pos_off[-1]], Stats):
+        pos[pos_off[k]:pos_off[k+1]] are ALL text positions SA[ep], SA[ep-1], .. of read k's longest matching suffix
+        when it has at least min_len bases (at most max_per_read of them when that is not 0), none otherwise.
+        A first call sizes pos, a second fills it."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        n_reads = max(read_off.size - 1, 0)
+        mlen = np.zeros(n_reads, np.uint32)
+        occ = np.zeros(n_reads, np.uint64)
+        pos_off = np.zeros(n_reads + 1, np.uint64)
+        st = Stats()
+        head = (self._h, bases.ctypes.data, read_off.ctypes.data, n_reads, int(min_len), int(max_per_read), mlen.ctypes.data,
+                occ.ctypes.data, pos_off.ctypes.data)
+        rc = lib().colbwt_locate_all_batch(*head, None, 0, C.byref(st))
+        if rc != 0 and not (rc == -1 and lib().colbwt_last_error().startswith(b"pos_cap too small")):
+            _check(rc)
+        pos = np.zeros(int(pos_off[-1]), np.uint64)
+        if rc != 0:
+            _check(lib().colbwt_locate_all_batch(*head, pos.ctypes.data, pos.size, C.byref(st)))
+        return mlen, occ, pos_off, pos, st
+
+    def locate_all(self, pattern, min_len=1, max_per_read=0):
+        """One read -> (mlen, occ, [positions]) as ints."""
+        p = np.frombuffer(bytes(pattern), dtype=np.uint8)
+        mlen, occ, _, pos, _ = self.locate_all_batch(p, np.array([0, p.size], np.uint64), min_len, max_per_read)
+        return int(mlen[0]), int(occ[0]), [int(x) for x in pos]
+
+    def locate_all_plan_device(self, d_bases, d_read_off, n_reads, n_bases, min_len, max_per_read, d_mlen, d_occ, d_pos_off, d_work,
+                               d_order=None, stream=0, want_total=True, timed=False):
+        """Search + plan on device buffers (raw device pointers, ints): fills d_mlen, d_occ, d_pos_off (n_reads + 1 u64)
+        and d_work (locate_all_work_bytes(n_reads) bytes, 256-byte aligned) -> (pos_off[n_reads] or None, Stats).
+        Asynchronous unless want_total or timed."""
+        st = Stats()
+        total = C.c_uint64(0)
+        _check(lib().colbwt_locate_all_plan_device(self._h, d_bases, d_read_off, n_reads, n_bases, int(min_len), int(max_per_read),
+                                                   d_mlen, d_occ, d_pos_off, d_work, d_order, stream,
+                                                   C.byref(total) if want_total else None, C.byref(st) if timed else None))
+        return (int(total.value) if want_total else None), st
+
+    def locate_all_fill_device(self, n_reads, read_lo, read_hi, d_pos_off, d_pos, pos_cap, d_work, stream=0, timed=False):
+        """The walk of the reads [read_lo, read_hi) of a planned batch into d_pos[0 .. pos_cap) (raw device pointers):
+        slot 0 is pos[pos_off[read_lo]]; nothing at or past pos_cap is written."""
+        st = Stats()
+        _check(lib().colbwt_locate_all_fill_device(self._h, n_reads, read_lo, read_hi, d_pos_off, d_pos, int(pos_cap), d_work, stream,
+                                                   C.byref(st) if timed else None))
+        return st
+
+    def locate_all_file(self, pattern_path, out_path=None, min_len=16, max_per_read=0, batch_bases=0):
+        """FASTA/FASTQ(.gz) -> text lines "name\tm\tmlen\tocc\tdoc:offset,.." with every position (default <pattern>.locate)."""
+        st = Stats()
+        _check(lib().colbwt_locate_all_file(self._h, os.fsencode(pattern_path), os.fsencode(out_path) if out_path else None,
+                                            int(min_len), int(max_per_read), batch_bases, C.byref(st)))
+        return st
+
     # -- docs: the documents holding each read's longest exact match (include/colbwt.h colbwt_docs_*) --
     def docs_mask_words(self):
         """W = ceil(n_docs / 64): u64 mask words per read (0 when no locate samples are attached)."""
@@ -470,6 +542,11 @@ def doc_offsets(positions, doc_start):
 def docs_work_bytes(n_reads):
     """colbwt_docs_work_bytes: size of the device workspace a docs_device call over n_reads reads needs."""
     return int(lib().colbwt_docs_work_bytes(int(n_reads)))
+
+
+def locate_all_work_bytes(n_reads):
+    """colbwt_locate_all_work_bytes: size of the device workspace a locate-all plan over n_reads reads needs."""
+    return int(lib().colbwt_locate_all_work_bytes(int(n_reads)))
 
 
 def _mask_docs(mask_row):

@@ -27,6 +27,7 @@
 #include "fasta_parallel.h"
 #include "fastx_reader.h"
 #include "index.h"
+#include "locate_all_query.h"
 #include "locate_query.h"
 #include "query_kernels.h"
 #include "seeds_reduce.h"
@@ -123,6 +124,7 @@ struct LocateTables {
         return DocsArgs{toe_row.as<const uint32_t>(), phi(), doc_dev.as<const uint32_t>(), n_docs(), min_len, max_walk};
     }
     PhiTable phi() const { return PhiTable{pair.as<const uint2>(), dir.as<const uint32_t>(), shift, (uint32_t)(n_buckets - 1)}; }
+    LocAllArgs all() const { return LocAllArgs{toe_row.as<const uint32_t>(), phi()}; }
     void reset() {
         toe_row.reset();
         pair.reset();
@@ -150,11 +152,17 @@ struct colbwt_index {
     void *stage[2] = {nullptr, nullptr};
     size_t stage_bytes = 0;
     LocateTables loc;
+    // The packed positions of a colbwt_locate_all_batch shard before they go to the host: their number
+    // is only known after the plan, so they have a buffer of their own, kept between calls.  One
+    // caller at a time uses it; concurrent callers allocate one for the call.
+    std::mutex all_mu;
+    DevPtr all_pos;
     ~colbwt_index() {
         for (colbwt_index *r : more) delete r;
         if (ix.device() >= 0) (void)hipSetDevice(ix.device());
         scratch.release();
         loc.reset();
+        all_pos.reset();
         for (void *p : stage)
             if (p) (void)hipHostFree(p);
     }
@@ -686,6 +694,151 @@ int docs_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *read
                                  part);
     if (rc == COLBWT_OK && doc_reads) std::copy(total.begin(), total.begin() + n_docs, doc_reads);
     if (rc == COLBWT_OK && doc_only) std::copy(total.begin() + n_docs, total.end(), doc_only);
+    return rc;
+}
+
+const char *kNoSamples = "no locate samples attached (colbwt_index_attach_locate)";
+const char *kTooManyReads = "more than 2^32-2 reads in a batch";
+
+// Where the shards of a colbwt_locate_all_batch call meet: a shard's positions start behind those of
+// the reads before it, and nothing may be written unless the whole batch fits, so every shard
+// publishes the number of its positions and waits for the others'.  The shards are disjoint and
+// cover the batch, so "all published" is "as many reads published as the batch has".  A shard that
+// fails before it publishes releases the others, which then leave without filling.
+struct LocAllShards {
+    struct Done {
+        uint64_t lo, hi, total;
+    };
+    std::mutex mu;
+    std::condition_variable cv;
+    std::vector<Done> done;
+    bool failed = false;
+    uint64_t n_reads = 0;
+    // -> false when a shard failed; else `base` = the positions of the reads before `lo`, `all` = the batch's
+    bool publish(uint64_t lo, uint64_t hi, uint64_t total, uint64_t &base, uint64_t &all) {
+        std::unique_lock<std::mutex> lk(mu);
+        done.push_back(Done{lo, hi, total});
+        cv.notify_all();
+        for (;;) {
+            if (failed) return false;
+            uint64_t covered = 0;
+            base = all = 0;
+            for (const Done &d : done) {
+                covered += d.hi - d.lo;
+                all += d.total;
+                if (d.hi <= lo) base += d.total;
+            }
+            if (covered == n_reads) return true;
+            cv.wait(lk);
+        }
+    }
+    void fail() {
+        std::lock_guard<std::mutex> g(mu);
+        failed = true;
+        cv.notify_all();
+    }
+};
+
+struct EventPair {
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~EventPair() {
+        for (hipEvent_t x : e)
+            if (x) (void)hipEventDestroy(x);
+    }
+    hipError_t create() {
+        hipError_t r = hipSuccess;
+        for (hipEvent_t &x : e)
+            if (r == hipSuccess && !x) r = hipEventCreate(&x);
+        return r;
+    }
+};
+
+// Locate-all (locate_all_query.h) for a batch in host memory: per shard the search and the plan, then
+// -- once every shard knows where its positions start and that the batch fits pos_cap -- the walk into
+// a buffer of the shard's size and the copy into the caller's packed array.  mlen, occ and pos_off are
+// filled whenever the search ran; pos only when pos_off[n_reads] <= pos_cap.
+int locate_all_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t min_len,
+                         uint64_t max_per_read, uint32_t *mlen, uint64_t *occ, uint64_t *pos_off, uint64_t *pos, uint64_t pos_cap,
+                         colbwt_stats *stats) {
+    if (idx) {
+        if (min_len == 0) return fail(COLBWT_ERR_ARG, "min_len must be at least 1");
+        if (!idx->loc.ready()) return fail(COLBWT_ERR_ARG, kNoSamples);
+        for (colbwt_index *r : idx->more)
+            if (!r->loc.ready()) return fail(COLBWT_ERR_ARG, kNoSamples);
+        if (n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, kTooManyReads);
+        if (n_reads == 0 && pos_off) pos_off[0] = 0;
+    }
+    auto bad_pointers = [&](uint64_t n_bases) -> const char * {
+        if ((n_bases && !bases) || !mlen || !occ || !pos_off) return "null bases/mlen/occ/pos_off";
+        return pos_cap && !pos ? "null pos with pos_cap > 0" : nullptr;
+    };
+    LocAllShards shards;
+    shards.n_reads = n_reads;
+    auto part = [&](colbwt_index *rep, uint64_t lo, uint64_t hi, uint64_t max_len, uint64_t min_read, colbwt_stats *st,
+                    std::string &msg) {
+        struct Guard {
+            LocAllShards &s;
+            bool armed = true;
+            ~Guard() { if (armed) s.fail(); }
+        } guard{shards};
+        const uint64_t n = hi - lo, off0 = read_off[lo];
+        const uint64_t work = locate_all_work_bytes(n);
+        const uint64_t out_bytes[2] = {n * sizeof(uint32_t), work + (2 * n + 1) * sizeof(uint64_t)};   // mlen; workspace, occ, pos_off
+        hipError_t launched = hipSuccess;
+        EventPair walk;
+        bool walked = false;
+        auto launch = [&](const DeviceBatch &b) {
+            uint64_t *d_occ = (uint64_t *)((uint8_t *)b.out[1] + work);
+            launched = launch_locate_all_plan(rep->ix, rep->loc.all(), b.bases, b.off, n, min_len, max_per_read, (uint32_t *)b.out[0],
+                                              d_occ, d_occ + n, b.out[1], b.order, b.stream);
+        };
+        auto fetch = [&](const DeviceBatch &b) {
+            TRY_HIP(launched, b.stream, msg);
+            const uint64_t *d_occ = (const uint64_t *)((const uint8_t *)b.out[1] + work), *d_off = d_occ + n;
+            TRY_HIP(hipMemcpyAsync(mlen + lo, b.out[0], n * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            TRY_HIP(hipMemcpyAsync(occ + lo, d_occ, n * sizeof(uint64_t), hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            TRY_HIP(hipMemcpyAsync(pos_off + lo + 1, d_off + 1, n * sizeof(uint64_t), hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            TRY_HIP(hipStreamSynchronize(b.stream), b.stream, msg);
+            const uint64_t total = pos_off[hi];          // still counted from the shard's first read
+            uint64_t base = 0, all = 0;
+            const bool go = shards.publish(lo, hi, total, base, all);
+            guard.armed = false;
+            if (!go) return COLBWT_OK;                   // the failing shard reports
+            if (base)
+                for (uint64_t k = lo + 1; k <= hi; ++k) pos_off[k] += base;
+            if (all > pos_cap || total == 0) return COLBWT_OK;
+            std::unique_lock<std::mutex> lease(rep->all_mu, std::defer_lock);
+            DevPtr own;
+            DevPtr &buf = lease.try_lock() ? rep->all_pos : own;
+            if (buf.bytes() < total * sizeof(uint64_t)) {
+                buf.reset();
+                TRY_HIP(buf.alloc(total * sizeof(uint64_t) + total + 4096), b.stream, msg);
+            }
+            TRY_HIP(walk.create(), b.stream, msg);
+            TRY_HIP(hipEventRecord(walk.e[0], b.stream), b.stream, msg);
+            launch_locate_all_fill(rep->ix, rep->loc.all(), n, 0, n, d_off, buf.as<uint64_t>(), total, b.out[1], b.stream);
+            TRY_HIP(hipGetLastError(), b.stream, msg);
+            TRY_HIP(hipEventRecord(walk.e[1], b.stream), b.stream, msg);
+            TRY_HIP(hipMemcpyAsync(pos + base, buf.get(), total * sizeof(uint64_t), hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            TRY_HIP(hipStreamSynchronize(b.stream), b.stream, msg);   // the buffer's lease ends with this call
+            walked = true;
+            return COLBWT_OK;
+        };
+        const int rc = replica_batch(rep, bases + off0, read_off + lo, off0, n, max_len, min_read, true, out_bytes, 0, st, msg, launch,
+                                     fetch);
+        if (rc == COLBWT_OK && walked) {                  // kernel_ms: search and scans + the walk
+            float ms = 0;
+            TRY_HIP(hipEventElapsedTime(&ms, walk.e[0], walk.e[1]), nullptr, msg);
+            st->kernel_ms += ms;
+            st->d2h_ms = std::max(0.0, st->d2h_ms - ms);
+        }
+        return rc;
+    };
+    if (idx && n_reads && pos_off) pos_off[0] = 0;
+    const int rc = sharded_batch(idx, read_off, n_reads, 0xFFFFFFFFull, "read longer than 2^32-1 bases", true, stats, bad_pointers,
+                                 part);
+    if (rc == COLBWT_OK && n_reads && pos_off[n_reads] > pos_cap)
+        return fail(COLBWT_ERR_ARG, "pos_cap too small: the batch has " + std::to_string(pos_off[n_reads]) + " positions (pos_off[n_reads])");
     return rc;
 }
 
@@ -1577,6 +1730,201 @@ int colbwt_locate_file(colbwt_index *idx, const char *pattern_path, const char *
     if (batch_bases == 0)   // the default batch of the file query, cut so that max_occ slots per read stay ~tens of MB
         batch_bases = std::max<uint64_t>(1ull << 20, (64ull << 20) * (1 + idx->more.size()) * 16 / std::max<uint32_t>(16, max_occ));
     return query_file_impl(idx, pattern_path, out, out, batch_bases, stats, false, true, max_occ);
+}
+
+uint32_t colbwt_locate_all_tile(void) { return kLocAllTile; }
+
+uint64_t colbwt_locate_all_work_bytes(uint64_t n_reads) { return locate_all_work_bytes(n_reads); }
+
+int colbwt_locate_all_plan_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads,
+                                  uint64_t n_bases, uint32_t min_len, uint64_t max_per_read, uint32_t *d_mlen, uint64_t *d_occ,
+                                  uint64_t *d_pos_off, void *d_work, const uint32_t *d_order, void *hip_stream, uint64_t *total,
+                                  colbwt_stats *stats) {
+    auto bad_argument = [&]() -> const char * {
+        if (min_len == 0) return "min_len must be at least 1";
+        if (!idx->loc.ready()) return kNoSamples;
+        for (colbwt_index *r : idx->more)
+            if (!r->loc.ready()) return kNoSamples;
+        if (n_reads == 0) return nullptr;
+        if (!d_bases || !d_read_off || !d_mlen || !d_occ) return "null device pointer";
+        if (((uintptr_t)d_bases & 15) || ((uintptr_t)d_mlen & 3) || ((uintptr_t)d_occ & 7))
+            return "d_bases must be 16-byte aligned, d_mlen 4-byte and d_occ 8-byte aligned";
+        if (n_reads >= 0xFFFFFFFFull) return kTooManyReads;
+        if (!d_pos_off || !d_work) return "null d_pos_off/d_work";
+        if ((uintptr_t)d_pos_off & 7) return "d_pos_off must be 8-byte aligned";
+        if ((uintptr_t)d_work & 255) return "d_work must be 256-byte aligned";
+        return nullptr;
+    };
+    hipError_t launched = hipSuccess;
+    const int rc = device_entry(idx, d_bases, n_reads, n_bases, hip_stream, 0, stats, bad_argument,
+                                [&](const Index &ix, hipStream_t stream) {
+                                    const LocateTables &L = replica_for(idx, d_bases)->loc;
+                                    launched = launch_locate_all_plan(ix, L.all(), d_bases, d_read_off, n_reads, min_len, max_per_read,
+                                                                      d_mlen, d_occ, d_pos_off, d_work, d_order, stream);
+                                });
+    if (rc != COLBWT_OK) return rc;
+    if (launched != hipSuccess) return hip_failed(launched, "colbwt_locate_all_plan_device", nullptr, g_err);
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    if (n_reads == 0) {                     // no reads: the offsets are the single 0
+        if (d_pos_off) TRY_HIP(hipMemsetAsync(d_pos_off, 0, sizeof(uint64_t), stream), nullptr, g_err);
+        if (total) {
+            *total = 0;
+            TRY_HIP(hipStreamSynchronize(stream), nullptr, g_err);
+        }
+        return COLBWT_OK;
+    }
+    if (total) {
+        TRY_HIP(hipMemcpyAsync(total, d_pos_off + n_reads, sizeof(uint64_t), hipMemcpyDeviceToHost, stream), nullptr, g_err);
+        TRY_HIP(hipStreamSynchronize(stream), nullptr, g_err);
+    }
+    return COLBWT_OK;
+}
+
+int colbwt_locate_all_fill_device(colbwt_index *idx, uint64_t n_reads, uint64_t read_lo, uint64_t read_hi, const uint64_t *d_pos_off,
+                                  uint64_t *d_pos, uint64_t pos_cap, const void *d_work, void *hip_stream, colbwt_stats *stats) {
+    auto bad_argument = [&]() -> const char * {
+        if (!idx->loc.ready()) return kNoSamples;
+        for (colbwt_index *r : idx->more)
+            if (!r->loc.ready()) return kNoSamples;
+        if (read_lo > read_hi || read_hi > n_reads) return "read_lo <= read_hi <= n_reads expected";
+        if (n_reads >= 0xFFFFFFFFull) return kTooManyReads;
+        if (read_lo == read_hi) return nullptr;
+        if (!d_pos_off || !d_work) return "null d_pos_off/d_work";
+        if (pos_cap && !d_pos) return "null d_pos with pos_cap > 0";
+        if (((uintptr_t)d_pos_off & 7) || ((uintptr_t)d_pos & 7)) return "d_pos_off and d_pos must be 8-byte aligned";
+        if ((uintptr_t)d_work & 255) return "d_work must be 256-byte aligned";
+        return nullptr;
+    };
+    return device_entry(idx, d_work, read_hi - read_lo, 0, hip_stream, 0, stats, bad_argument,
+                        [&](const Index &ix, hipStream_t stream) {
+                            const LocateTables &L = replica_for(idx, d_work)->loc;
+                            launch_locate_all_fill(ix, L.all(), n_reads, read_lo, read_hi, d_pos_off, d_pos, pos_cap, d_work, stream);
+                        });
+}
+
+int colbwt_locate_all_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t min_len,
+                            uint64_t max_per_read, uint32_t *mlen, uint64_t *occ, uint64_t *pos_off, uint64_t *pos, uint64_t pos_cap,
+                            colbwt_stats *stats) {
+    return locate_all_batch_all(idx, bases, read_off, n_reads, min_len, max_per_read, mlen, occ, pos_off, pos, pos_cap, stats);
+}
+
+// One batch at a time on the handle's first replica: reader, plan, then fill / copy / write in read
+// ranges of at most COLBWT_LOCATE_ALL_FILE_POSITIONS positions.
+int colbwt_locate_all_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t min_len, uint64_t max_per_read,
+                           uint64_t batch_bases, colbwt_stats *stats) {
+    if (!idx || !pattern_path) return fail(COLBWT_ERR_ARG, "null argument");
+    if (min_len == 0) return fail(COLBWT_ERR_ARG, "min_len must be at least 1");
+    if (!idx->loc.ready()) return fail(COLBWT_ERR_ARG, kNoSamples);
+    if (stats) memset(stats, 0, sizeof(*stats));
+    const std::string out = out_path ? out_path : std::string(pattern_path) + ".locate";
+    if (batch_bases == 0) batch_bases = 64ull << 20;
+    FastxReader reader;
+    if (!reader.open(pattern_path)) return fail(COLBWT_ERR_IO, std::string("cannot open pattern file ") + pattern_path);
+    int rc = select_device(idx->ix.device(), g_err);
+    if (rc != COLBWT_OK) return rc;
+    struct File {
+        FILE *f = nullptr;
+        ~File() { if (f) fclose(f); }
+    } wn;
+    wn.f = fopen(out.c_str(), "wb");
+    if (!wn.f) return fail(COLBWT_ERR_IO, "cannot create " + out);
+    setvbuf(wn.f, nullptr, _IOFBF, 4u << 20);
+    struct Stream {
+        hipStream_t s = nullptr;
+        ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    } st;
+    TRY_HIP(hipStreamCreateWithFlags(&st.s, hipStreamNonBlocking), nullptr, g_err);
+    const hipStream_t stream = st.s;
+    const uint64_t cap = COLBWT_LOCATE_ALL_FILE_POSITIONS;
+    const std::vector<uint64_t> &ds = idx->loc.doc_start;
+
+    DevPtr d_bases, d_off, d_mlen, d_occ, d_pos_off, d_work, d_pos;
+    auto need = [](DevPtr &p, uint64_t bytes) { return p.bytes() >= bytes ? hipSuccess : p.alloc(bytes + bytes / 8 + 256); };
+    std::vector<uint8_t> bases;
+    std::vector<uint64_t> off, occ, pos_off, pos;
+    std::vector<uint32_t> mlen;
+    std::vector<std::string> names;
+    std::string name;
+    bool ok = true;
+    for (bool more = true; more;) {
+        bases.clear();
+        names.clear();
+        off.assign(1, 0);
+        while (bases.size() < batch_bases && names.size() < 0xFFFFFFFEull) {
+            if (!reader.next(name, bases)) {
+                more = false;
+                break;
+            }
+            if (bases.size() - off.back() > 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, "read longer than 2^32-1 bases");
+            names.push_back(name);
+            off.push_back(bases.size());
+        }
+        const uint64_t n = names.size(), nb = bases.size();
+        if (n == 0) continue;
+        const uint64_t bases_alloc = (nb + 64 + 63) & ~63ull;     // the search reads whole 64-byte blocks
+        TRY_HIP(need(d_bases, bases_alloc), stream, g_err);
+        TRY_HIP(need(d_off, 8 * (n + 1)), stream, g_err);
+        TRY_HIP(need(d_mlen, 4 * n), stream, g_err);
+        TRY_HIP(need(d_occ, 8 * n), stream, g_err);
+        TRY_HIP(need(d_pos_off, 8 * (n + 1)), stream, g_err);
+        TRY_HIP(need(d_work, locate_all_work_bytes(n)), stream, g_err);
+        TRY_HIP(hipMemsetAsync(d_bases.as<uint8_t>() + nb, 0, bases_alloc - nb, stream), stream, g_err);
+        if (nb) TRY_HIP(hipMemcpyAsync(d_bases.get(), bases.data(), nb, hipMemcpyHostToDevice, stream), stream, g_err);
+        TRY_HIP(hipMemcpyAsync(d_off.get(), off.data(), 8 * (n + 1), hipMemcpyHostToDevice, stream), stream, g_err);
+        colbwt_stats ps{}, fs{};
+        uint64_t total = 0;
+        rc = colbwt_locate_all_plan_device(idx, d_bases.as<uint8_t>(), d_off.as<uint64_t>(), n, nb, min_len, max_per_read,
+                                           d_mlen.as<uint32_t>(), d_occ.as<uint64_t>(), d_pos_off.as<uint64_t>(), d_work.get(), nullptr,
+                                           stream, &total, &ps);
+        if (rc != COLBWT_OK) return rc;
+        mlen.resize(n);
+        occ.resize(n);
+        pos_off.resize(n + 1);
+        TRY_HIP(hipMemcpyAsync(mlen.data(), d_mlen.get(), 4 * n, hipMemcpyDeviceToHost, stream), stream, g_err);
+        TRY_HIP(hipMemcpyAsync(occ.data(), d_occ.get(), 8 * n, hipMemcpyDeviceToHost, stream), stream, g_err);
+        TRY_HIP(hipMemcpyAsync(pos_off.data(), d_pos_off.get(), 8 * (n + 1), hipMemcpyDeviceToHost, stream), stream, g_err);
+        TRY_HIP(hipStreamSynchronize(stream), stream, g_err);
+        const uint64_t room = std::min(total, cap);
+        TRY_HIP(need(d_pos, 8 * std::max<uint64_t>(room, 1)), stream, g_err);
+        pos.resize(room);
+        if (stats) {
+            stats->n_reads += n;
+            stats->n_bases += nb;
+            stats->kernel_ms += ps.kernel_ms;
+        }
+        for (uint64_t lo = 0; lo < n && ok;) {
+            uint64_t hi = lo;
+            while (hi < n && pos_off[hi + 1] - pos_off[lo] <= cap) ++hi;
+            if (hi == lo)
+                return fail(COLBWT_ERR_NOMEM, "read " + names[lo] + " has " + std::to_string(pos_off[lo + 1] - pos_off[lo]) +
+                                                  " positions, more than colbwt_locate_all_file holds at once (" + std::to_string(cap) +
+                                                  "): set max_per_read");
+            const uint64_t cnt = pos_off[hi] - pos_off[lo];
+            if (cnt) {
+                rc = colbwt_locate_all_fill_device(idx, n, lo, hi, d_pos_off.as<uint64_t>(), d_pos.as<uint64_t>(), cnt, d_work.get(), stream,
+                                                   &fs);
+                if (rc != COLBWT_OK) return rc;
+                TRY_HIP(hipMemcpyAsync(pos.data(), d_pos.get(), 8 * cnt, hipMemcpyDeviceToHost, stream), stream, g_err);
+                TRY_HIP(hipStreamSynchronize(stream), stream, g_err);
+                if (stats) stats->kernel_ms += fs.kernel_ms;
+            }
+            for (uint64_t k = lo; k < hi && ok; ++k) {
+                ok = fprintf(wn.f, "%s\t%llu\t%u\t%llu\t", names[k].c_str(), (unsigned long long)(off[k + 1] - off[k]), mlen[k],
+                             (unsigned long long)occ[k]) > 0;
+                for (uint64_t t = 0, w = pos_off[k + 1] - pos_off[k]; t < w && ok; ++t) {
+                    const uint64_t x = pos[pos_off[k] - pos_off[lo] + t];
+                    const size_t d = (size_t)(std::upper_bound(ds.begin(), ds.end(), x) - ds.begin()) - 1;
+                    ok = fprintf(wn.f, t ? ",%zu:%llu" : "%zu:%llu", d, (unsigned long long)(x - ds[d])) > 0;
+                }
+                ok = ok && fputc('\n', wn.f) != EOF;
+            }
+            lo = hi;
+        }
+    }
+    FILE *f = wn.f;
+    wn.f = nullptr;
+    if (fclose(f) != 0 || !ok) return fail(COLBWT_ERR_IO, "short write on " + out);
+    return COLBWT_OK;
 }
 
 uint32_t colbwt_docs_mask_words(const colbwt_index *idx) {

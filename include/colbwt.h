@@ -242,7 +242,7 @@ int colbwt_count_file(colbwt_index *idx, const char *pattern_path, const char *o
  * such a byte mlen and occ equal count's.  With k = min(occ, max_occ), the read's max_occ result
  * slots hold SA[ep], SA[ep-1], .., SA[ep-k+1]: the start positions in the indexed text of
  * occurrences of P[m-mlen..m), in suffix-array order from the range's last suffix down; the slots
- * past k hold COLBWT_LOCATE_NONE.  There is no "all occurrences" mode.
+ * past k hold COLBWT_LOCATE_NONE.  Every occurrence: colbwt_locate_all_* below.
  *
  * Samples: <prefix>.col_loc, written by the builder (colbwt_rlbwt_build_files_locate, build_rlbwt -L,
  * col-bwt build --locate); they cannot be rebuilt from a .col_pml.  Little-endian:
@@ -278,6 +278,64 @@ int colbwt_locate_device(colbwt_index *idx, const uint8_t *d_bases, const uint64
                          const uint32_t *d_order, void *hip_stream, colbwt_stats *stats);
 int colbwt_locate_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t max_occ,
                        uint64_t batch_bases, colbwt_stats *stats);
+
+/* ---- locate-all: every occurrence of each read's longest exact match, as compressed sparse rows ----
+ * colbwt_locate_* reports at most max_occ positions per read in n_reads * max_occ slots; here a read
+ * gets exactly as many slots as it has positions: one offset array, one packed position array.  The
+ * search is exactly colbwt_locate_*'s (a read byte <= 1 ends it); mlen and occ are reported for every
+ * read.  Parameters min_len >= 1 and max_per_read, where 0 means no cap; locate samples must be attached.
+ *   walked   w = occ (min(occ, max_per_read) when max_per_read != 0) when mlen >= min_len, else w = 0.
+ *   pos_off  n_reads + 1 u64 entries: pos_off[0] = 0, pos_off[k+1] = pos_off[k] + w_k.
+ *   pos      read k owns pos[pos_off[k] .. pos_off[k+1]): SA[ep], SA[ep-1], .., SA[ep-w+1] as u64 --
+ *            locate's order, so the first min(w, K) entries equal what colbwt_locate_batch returns at
+ *            max_occ = K.  No slot holds COLBWT_LOCATE_NONE.
+ * The output is deterministic: every slot has one writer and no atomics are involved.
+ *
+ * On the device the work is split in two.  colbwt_locate_all_plan_device runs the search and two scans:
+ * it fills d_mlen, d_occ (n_reads entries) and d_pos_off (n_reads + 1), and leaves per-read state (the
+ * BWT position of ep, SA[ep], tile offsets) in d_work: 256-byte aligned,
+ * colbwt_locate_all_work_bytes(n_reads) bytes, a function of n_reads alone.  It is asynchronous on
+ * `hip_stream` unless `total` or `stats` is given; with `total` (host, nullable) it synchronises the
+ * stream and stores pos_off[n_reads], the size the position array needs.  colbwt_locate_all_fill_device
+ * then walks the positions of the reads [read_lo, read_hi) of that batch into d_pos[0 ..): slot 0 is
+ * pos[pos_off[read_lo]], so a caller with little memory fills in pieces.  It must find d_work and
+ * d_pos_off as the plan left them, allocates nothing, reads its bounds from device memory (no host
+ * read-back) and runs a grid of fixed size whose lanes stride over the range's tiles: a read's range
+ * is cut into tiles of colbwt_locate_all_tile() positions (256 unless the library was built otherwise),
+ * each restarted from the SA sample at the nearest end of a BWT run at or below its start and walked
+ * by one lane, so one read of a million occurrences is thousands of short walks and not one long one.
+ * Nothing at or past d_pos[pos_cap] is ever written: the kernel guards every store, and a range that
+ * needs more than pos_cap slots is cut off there without an error (size d_pos from pos_off).  Several
+ * fills of one plan may be in flight at once.  Arguments, alignment (d_pos_off / d_pos 8-byte), error
+ * codes and d_order (search only) as colbwt_locate_device / colbwt_docs_device; "no locate samples
+ * attached" is COLBWT_ERR_ARG; the fill addresses the replica on d_work's device.  kernel_ms of the plan
+ * covers the search and the scans, kernel_ms of the fill the walk.  Fewer than 2^32-1 reads per call.
+ *
+ * colbwt_locate_all_batch: reads in host memory, sharded over the replicas as colbwt_locate_batch
+ * shards them; the shards' offsets are rebased on the host.  mlen, occ and pos_off are filled whenever
+ * the search ran.  When pos_off[n_reads] > pos_cap the call returns COLBWT_ERR_ARG ("pos_cap too
+ * small") with those three filled and pos untouched (pos may be NULL with pos_cap 0): the sizing
+ * convention of colbwt_build_col_pml_arrays.  kernel_ms is the sum of plan and fill.
+ * colbwt_locate_all_file: FASTA/FASTQ(.gz) in, the lines of colbwt_locate_file out
+ * ("name\tm\tmlen\tocc\tdoc:offset,..\n") with all w positions of every read (the last field is empty
+ * when w == 0); out_path NULL => pattern + ".locate".  It plans a batch of batch_bases bases (0: 64 M) on
+ * the handle's first replica, then fills, copies and writes it in read ranges, so that it never holds
+ * more than COLBWT_LOCATE_ALL_FILE_POSITIONS positions at once; a single read with more fails with
+ * COLBWT_ERR_NOMEM and a message that names max_per_read. */
+#define COLBWT_LOCATE_ALL_FILE_POSITIONS ((uint64_t)1 << 24)
+uint32_t colbwt_locate_all_tile(void);
+uint64_t colbwt_locate_all_work_bytes(uint64_t n_reads);
+int colbwt_locate_all_plan_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads,
+                                  uint64_t n_bases, uint32_t min_len, uint64_t max_per_read, uint32_t *d_mlen, uint64_t *d_occ,
+                                  uint64_t *d_pos_off, void *d_work, const uint32_t *d_order, void *hip_stream, uint64_t *total,
+                                  colbwt_stats *stats);
+int colbwt_locate_all_fill_device(colbwt_index *idx, uint64_t n_reads, uint64_t read_lo, uint64_t read_hi, const uint64_t *d_pos_off,
+                                  uint64_t *d_pos, uint64_t pos_cap, const void *d_work, void *hip_stream, colbwt_stats *stats);
+int colbwt_locate_all_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t min_len,
+                            uint64_t max_per_read, uint32_t *mlen, uint64_t *occ, uint64_t *pos_off, uint64_t *pos, uint64_t pos_cap,
+                            colbwt_stats *stats);
+int colbwt_locate_all_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t min_len, uint64_t max_per_read,
+                           uint64_t batch_bases, colbwt_stats *stats);
 
 /* ---- seeds: per-read PML peaks and chain summaries, reduced on the device -----------------
  * What read classification consumes of a query's output, so that tens of bytes per read leave the
