@@ -38,12 +38,17 @@ EXPORTS = (
     "colbwt_docs_mask_words", "colbwt_docs_work_bytes", "colbwt_docs_batch", "colbwt_docs_device", "colbwt_docs_file",
     "colbwt_locate_all_tile", "colbwt_locate_all_work_bytes", "colbwt_locate_all_plan_device", "colbwt_locate_all_fill_device",
     "colbwt_locate_all_batch", "colbwt_locate_all_file",
+    "colbwt_anchors_device", "colbwt_anchors_batch", "colbwt_anchors_file",
 )
 
 SEED_NONE = 0xFFFFFFFF          # include/colbwt.h COLBWT_SEED_NONE: seed_pos of a slot past the read's min(n_seeds, max_seeds)
 # colbwt_seed_summary as a numpy record: one per read
 SEED_SUMMARY = np.dtype([(k, np.uint32) for k in ("n_seeds", "max_len", "cov", "resets", "n_col", "col_cov", "asc", "desc")])
 LOCATE_NONE = (1 << 64) - 1     # include/colbwt.h COLBWT_LOCATE_NONE: a position slot past the read's min(occ, max_occ)
+ANCHOR_NONE = 0xFFFFFFFF        # include/colbwt.h COLBWT_ANCHOR_NONE: anchor_start of a slot past the read's n_stored
+# colbwt_anchor_summary as a numpy record: one per read
+AnchorSummary = np.dtype([(k, np.uint32) for k in ("n_factors", "max_len", "skipped", "n_kept", "cov", "n_unique", "cov_unique",
+                                                   "n_stored")])
 
 
 class ColbwtError(RuntimeError):
@@ -152,6 +157,9 @@ def lib():
     L.colbwt_locate_all_fill_device.argtypes = [vp, u64, u64, u64, vp, vp, u64, vp, vp, C.POINTER(Stats)]
     L.colbwt_locate_all_batch.argtypes = [vp, vp, vp, u64, u32, u64, vp, vp, vp, vp, u64, C.POINTER(Stats)]
     L.colbwt_locate_all_file.argtypes = [vp, C.c_char_p, C.c_char_p, u32, u64, u64, C.POINTER(Stats)]
+    L.colbwt_anchors_device.argtypes = [vp, vp, vp, u64, u64, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Stats)]
+    L.colbwt_anchors_batch.argtypes = [vp, vp, vp, u64, u32, u32, u32, vp, vp, vp, vp, vp, C.POINTER(Stats)]
+    L.colbwt_anchors_file.argtypes = [vp, C.c_char_p, C.c_char_p, u32, u32, u32, u64, C.POINTER(Stats)]
     _lib = L
     return L
 
@@ -453,6 +461,55 @@ class ColPml:
         st = Stats()
         _check(lib().colbwt_locate_all_file(self._h, os.fsencode(pattern_path), os.fsencode(out_path) if out_path else None,
                                             int(min_len), int(max_per_read), batch_bases, C.byref(st)))
+        return st
+
+    # -- anchors: left-maximal exact matches along the whole read (include/colbwt.h colbwt_anchors_*) --
+    def anchors_batch(self, bases, read_off, min_len=16, max_anchors=16, max_occ=1, want_slots=True):
+        """Many reads -> (summary, start, len, occ, pos, Stats): summary an AnchorSummary record per read; start / len
+        (uint32) and occ (uint64) are (n_reads, max_anchors), largest start first, unused slots ANCHOR_NONE / 0 / 0; pos
+        (uint64) is (n_reads, max_anchors, max_occ) with LOCATE_NONE past min(occ, max_occ), or None when max_occ == 0
+        (which needs no locate samples).  Not want_slots: summaries only, the four arrays None."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        n_reads = max(read_off.size - 1, 0)
+        k, w = max(int(max_anchors), 0), max(int(max_occ), 0)
+        summary = np.zeros(n_reads, AnchorSummary)
+        start = np.zeros((n_reads, k), np.uint32) if want_slots else None
+        ln = np.zeros((n_reads, k), np.uint32) if want_slots else None
+        occ = np.zeros((n_reads, k), np.uint64) if want_slots else None
+        pos = np.zeros((n_reads, k, w), np.uint64) if want_slots and w else None
+        st = Stats()
+        _check(lib().colbwt_anchors_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n_reads, int(min_len), int(max_anchors),
+                                          int(max_occ), summary.ctypes.data,
+                                          *((a.ctypes.data if a is not None else None) for a in (start, ln, occ, pos)), C.byref(st)))
+        return summary, start, ln, occ, pos, st
+
+    def anchors(self, pattern, min_len=16, max_anchors=16, max_occ=1):
+        """One read -> (summary dict, [(start, len, occ, [positions]), ..] largest start first)."""
+        p = np.frombuffer(bytes(pattern), dtype=np.uint8)
+        summary, start, ln, occ, pos, _ = self.anchors_batch(p, np.array([0, p.size], np.uint64), min_len, max_anchors, max_occ)
+        out = []
+        for t in range(int(summary["n_stored"][0])):
+            k = min(int(occ[0, t]), int(max_occ))
+            out.append((int(start[0, t]), int(ln[0, t]), int(occ[0, t]), [int(x) for x in pos[0, t, :k]] if k else []))
+        return {f: int(summary[f][0]) for f in AnchorSummary.names}, out
+
+    def anchors_device(self, d_bases, d_read_off, n_reads, n_bases, min_len, max_anchors, max_occ, d_summary, d_start=None,
+                       d_len=None, d_occ=None, d_pos=None, d_order=None, stream=0, timed=False):
+        """Device-resident anchors entry point: raw device pointers (ints).  d_start / d_len / d_occ all or none; d_pos
+        (n_reads * max_anchors * max_occ u64) exactly when they are given and max_occ > 0."""
+        st = Stats()
+        _check(lib().colbwt_anchors_device(self._h, d_bases, d_read_off, n_reads, n_bases, int(min_len), int(max_anchors),
+                                           int(max_occ), d_summary, d_start, d_len, d_occ, d_pos, d_order, stream,
+                                           C.byref(st) if timed else None))
+        return st
+
+    def anchors_file(self, pattern_path, out_path=None, min_len=16, max_anchors=16, max_occ=1, batch_bases=0):
+        """FASTA/FASTQ(.gz) -> text lines "name\tm\tn_factors\tn_kept\tcov\tmax_len\tskipped\tn_unique\tcov_unique\tA,A,..",
+        A = start:len:occ@doc:offset@.. (default <pattern>.anchors)."""
+        st = Stats()
+        _check(lib().colbwt_anchors_file(self._h, os.fsencode(pattern_path), os.fsencode(out_path) if out_path else None,
+                                         int(min_len), int(max_anchors), int(max_occ), batch_bases, C.byref(st)))
         return st
 
     # -- docs: the documents holding each read's longest exact match (include/colbwt.h colbwt_docs_*) --

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/colbwt.h"
+#include "anchors_query.h"
 #include "bin_writer.h"
 #include "count_query.h"
 #include "docs_query.h"
@@ -616,6 +617,97 @@ int locate_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *re
             return COLBWT_OK;
         };
         return replica_batch(rep, bases + off0, read_off + lo, off0, n, max_len, min_len, true, out_bytes, 0, st, msg, launch,
+                             fetch);
+    };
+    return sharded_batch(idx, read_off, n_reads, 0xFFFFFFFFull, "read longer than 2^32-1 bases", true, stats, bad_pointers,
+                         part);
+}
+
+// Largest max_anchors: slots are n_reads x max_anchors, as the seeds' are.
+constexpr uint32_t kAnchorsMaxSlots = 1u << 16;
+const char *kAnchorsSlotSet = "start/len/occ: all three or none; pos exactly when they are given and max_occ > 0";
+
+const char *anchors_bad_params(uint32_t min_len, uint32_t max_anchors, uint32_t max_occ) {
+    if (min_len == 0) return "min_len must be at least 1";
+    if (max_anchors == 0 || max_anchors > kAnchorsMaxSlots) return "max_anchors must be 1 .. 2^16";
+    if (max_occ > kLocateMaxOcc) return "max_occ must be 0 .. 2^20";
+    return nullptr;
+}
+
+// Parameters, then the samples (only max_occ > 0 needs them), then the slot pointer set.
+const char *anchors_bad_setup(const colbwt_index *idx, uint32_t min_len, uint32_t max_anchors, uint32_t max_occ, const void *start,
+                              const void *len, const void *occ, const void *pos) {
+    if (const char *m = anchors_bad_params(min_len, max_anchors, max_occ)) return m;
+    if (max_occ > 0) {
+        if (!idx->loc.ready()) return "no locate samples attached (colbwt_index_attach_locate)";
+        for (const colbwt_index *r : idx->more)
+            if (!r->loc.ready()) return "no locate samples attached (colbwt_index_attach_locate)";
+    }
+    if ((start != nullptr) != (len != nullptr) || (start != nullptr) != (occ != nullptr) ||
+        (pos != nullptr) != (start != nullptr && max_occ > 0))
+        return kAnchorsSlotSet;
+    return nullptr;
+}
+
+AnchorsArgs anchors_args(const colbwt_index *rep, uint32_t min_len, uint32_t max_anchors, uint32_t max_occ, void *summary,
+                         uint32_t *start, uint32_t *len, uint64_t *occ, uint64_t *pos) {
+    AnchorsArgs A{};
+    if (pos) {
+        A.toe_row = rep->loc.toe_row.as<const uint32_t>();
+        A.phi = rep->loc.phi();
+    }
+    A.min_len = min_len;
+    A.max_anchors = max_anchors;
+    A.max_occ = max_occ;
+    A.summary = (uint4 *)summary;
+    A.start = start;
+    A.len = len;
+    A.occ = occ;
+    A.pos = pos;
+    return A;
+}
+
+// Anchors (anchors_query.h) for a batch in host memory.  The first result array of the scratch holds the
+// summaries, then start and len of every slot; the second occ, then the positions.
+int anchors_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t min_len,
+                      uint32_t max_anchors, uint32_t max_occ, colbwt_anchor_summary *summary, uint32_t *start, uint32_t *len,
+                      uint64_t *occ, uint64_t *pos, colbwt_stats *stats) {
+    if (idx) {
+        if (const char *m = anchors_bad_setup(idx, min_len, max_anchors, max_occ, start, len, occ, pos)) return fail(COLBWT_ERR_ARG, m);
+        if (n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, "more than 2^32-2 reads in a batch");
+    }
+    const uint64_t K = max_anchors, W = pos ? max_occ : 0;
+    auto bad_pointers = [&](uint64_t n_bases) -> const char * {
+        return (n_bases && !bases) || !summary ? "null bases/summary" : nullptr;
+    };
+    auto part = [&](colbwt_index *rep, uint64_t lo, uint64_t hi, uint64_t max_len, uint64_t min_read, colbwt_stats *st,
+                    std::string &msg) {
+        const uint64_t n = hi - lo, off0 = read_off[lo], slots = start ? n * K : 0;
+        const uint64_t out_bytes[2] = {n * 32 + 2 * slots * sizeof(uint32_t), (slots + slots * W) * sizeof(uint64_t)};
+        auto launch = [&](const DeviceBatch &b) {
+            uint32_t *d_start = (uint32_t *)((uint8_t *)b.out[0] + n * 32);
+            uint64_t *d_occ = (uint64_t *)b.out[1];
+            launch_anchors(rep->ix,
+                           anchors_args(rep, min_len, max_anchors, max_occ, b.out[0], start ? d_start : nullptr,
+                                        start ? d_start + slots : nullptr, start ? d_occ : nullptr, pos ? d_occ + slots : nullptr),
+                           b.bases, b.off, n, b.order, b.stream);
+        };
+        auto fetch = [&](const DeviceBatch &b) {
+            const uint32_t *d_start = (const uint32_t *)((const uint8_t *)b.out[0] + n * 32);
+            const uint64_t *d_occ = (const uint64_t *)b.out[1];
+            TRY_HIP(hipMemcpyAsync(summary + lo, b.out[0], n * 32, hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            if (slots) {
+                TRY_HIP(hipMemcpyAsync(start + lo * K, d_start, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+                TRY_HIP(hipMemcpyAsync(len + lo * K, d_start + slots, slots * sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream), b.stream,
+                        msg);
+                TRY_HIP(hipMemcpyAsync(occ + lo * K, d_occ, slots * sizeof(uint64_t), hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            }
+            if (slots * W)
+                TRY_HIP(hipMemcpyAsync(pos + lo * K * W, d_occ + slots, slots * W * sizeof(uint64_t), hipMemcpyDeviceToHost, b.stream),
+                        b.stream, msg);
+            return COLBWT_OK;
+        };
+        return replica_batch(rep, bases + off0, read_off + lo, off0, n, max_len, min_read, true, out_bytes, 0, st, msg, launch,
                              fetch);
     };
     return sharded_batch(idx, read_off, n_reads, 0xFFFFFFFFull, "read longer than 2^32-1 bases", true, stats, bad_pointers,
@@ -1285,11 +1377,14 @@ int colbwt_query_device_ordered(colbwt_index *idx, const uint8_t *d_bases, const
 // "\tdoc:offset,doc:offset,..".  `seeds_k` > 0 (with `count`): seeds (seeds_reduce.h) with min_len =
 // seeds_min and max_seeds = seeds_k, one line per read as colbwt_seeds_file documents it.  `docs_w` > 0
 // (with `count`): docs (docs_query.h) with min_len = docs_min and max_walk = docs_w, one line per read
-// and, after the last batch, pml_name + ".tally", as colbwt_docs_file documents them.
+// and, after the last batch, pml_name + ".tally", as colbwt_docs_file documents them.  `anch_k` > 0 (with
+// `count`): anchors (anchors_query.h) with min_len = anch_min, max_anchors = anch_k and max_occ = anch_occ,
+// one line per read as colbwt_anchors_file documents it.
 static int query_file_impl(colbwt_index *idx, const char *pattern_path, const std::string &pml_name,
                            const std::string &cid_name, uint64_t batch_bases, colbwt_stats *stats, bool binary,
                            bool count = false, uint32_t locate_k = 0, uint32_t seeds_min = 0, uint32_t seeds_k = 0,
-                           uint32_t docs_min = 0, uint32_t docs_w = 0) {
+                           uint32_t docs_min = 0, uint32_t docs_w = 0, uint32_t anch_min = 0, uint32_t anch_k = 0,
+                           uint32_t anch_occ = 0) {
     if (stats) memset(stats, 0, sizeof(*stats));
     const uint32_t docs_n = docs_w ? idx->loc.n_docs() : 0, docs_words = docs_mask_words(docs_n);
     std::vector<uint64_t> docs_tally(2 * (size_t)docs_n, 0), docs_part(2 * (size_t)docs_n, 0);   // doc_reads, then doc_only
@@ -1399,6 +1494,31 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
                 free_q.push(b);
                 continue;
             }
+            if (anch_k) {
+                const uint32_t *sm = b->pml->as<uint32_t>();           // 8 words per read
+                const uint32_t *as = sm + 8 * n_reads, *al = as + n_reads * anch_k;
+                const uint64_t *ao = b->cid->as<uint64_t>(), *ap = ao + n_reads * anch_k;
+                const std::vector<uint64_t> &ds = idx->loc.doc_start;
+                for (uint64_t k = 0; k < n_reads && count_ok; ++k) {
+                    const uint32_t *q = sm + 8 * k;                    // n_factors max_len skipped n_kept cov n_unique cov_unique n_stored
+                    count_ok = fprintf(wn, "%s\t%llu\t%u\t%u\t%u\t%u\t%u\t%u\t%u\t", b->names[k].c_str(),
+                                       (unsigned long long)(b->off[k + 1] - b->off[k]), q[0], q[3], q[4], q[1], q[2], q[5], q[6]) > 0;
+                    for (uint64_t t = 0; t < q[7] && count_ok; ++t) {
+                        const uint64_t at = k * anch_k + t;
+                        count_ok = fprintf(wn, t ? ",%u:%u:%llu" : "%u:%u:%llu", as[at], al[at], (unsigned long long)ao[at]) > 0;
+                        const uint64_t want = std::min<uint64_t>(ao[at], anch_occ);
+                        for (uint64_t w = 0; w < want && count_ok; ++w) {
+                            const uint64_t x = ap[at * anch_occ + w];
+                            const size_t d = (size_t)(std::upper_bound(ds.begin(), ds.end(), x) - ds.begin()) - 1;
+                            count_ok = fprintf(wn, "@%zu:%llu", d, (unsigned long long)(x - ds[d])) > 0;
+                        }
+                    }
+                    count_ok = count_ok && fputc('\n', wn) != EOF;
+                }
+                t_format += now() - t0;
+                free_q.push(b);
+                continue;
+            }
             if (docs_w) {
                 const uint32_t *ml = b->pml->as<uint32_t>(), *nh = ml + n_reads;
                 const uint64_t *oc = b->cid->as<uint64_t>(), *mk = oc + n_reads;   // docs_words mask words per read
@@ -1472,7 +1592,10 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
             rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
         if (rc == COLBWT_OK && docs_w && (!b->pml->ensure(n_reads * 8) || !b->cid->ensure(n_reads * 8 * (1 + (uint64_t)docs_words))))
             rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
-        if (rc == COLBWT_OK && count && !seeds_k && !docs_w && (!b->pml->ensure(n_reads * 4) || !b->cid->ensure(n_reads * 8 * (1 + (uint64_t)locate_k))))
+        if (rc == COLBWT_OK && anch_k &&
+            (!b->pml->ensure(n_reads * (32 + 8 * (uint64_t)anch_k)) || !b->cid->ensure(n_reads * anch_k * 8 * (1 + (uint64_t)anch_occ))))
+            rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
+        if (rc == COLBWT_OK && count && !seeds_k && !docs_w && !anch_k && (!b->pml->ensure(n_reads * 4) || !b->cid->ensure(n_reads * 8 * (1 + (uint64_t)locate_k))))
             rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
         if (rc == COLBWT_OK && !count && (!b->cid->ensure(nb) || !b->pml->ensure(nb * (b->wide ? 4 : 2))))
             rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
@@ -1481,6 +1604,12 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
             uint32_t *sp = b->cid->as<uint32_t>(), *sl = sp + n_reads * seeds_k;
             rc = seeds_batch_all(idx, b->bases.data(), b->off.data(), n_reads, seeds_min, seeds_k, b->pml->as<uint32_t>(), sp, sl,
                                  (uint8_t *)(sl + n_reads * seeds_k), &st);
+        } else if (anch_k) {
+            uint32_t *as = b->pml->as<uint32_t>() + 8 * n_reads;
+            uint64_t *ao = b->cid->as<uint64_t>();
+            rc = anchors_batch_all(idx, b->bases.data(), b->off.data(), n_reads, anch_min, anch_k, anch_occ,
+                                   b->pml->as<colbwt_anchor_summary>(), as, as + n_reads * anch_k, ao,
+                                   anch_occ ? ao + n_reads * anch_k : nullptr, &st);
         } else if (docs_w) {
             rc = docs_batch_all(idx, b->bases.data(), b->off.data(), n_reads, docs_min, docs_w, b->pml->as<uint32_t>(),
                                 b->cid->as<uint64_t>(), b->pml->as<uint32_t>() + n_reads, b->cid->as<uint64_t>() + n_reads,
@@ -1730,6 +1859,49 @@ int colbwt_locate_file(colbwt_index *idx, const char *pattern_path, const char *
     if (batch_bases == 0)   // the default batch of the file query, cut so that max_occ slots per read stay ~tens of MB
         batch_bases = std::max<uint64_t>(1ull << 20, (64ull << 20) * (1 + idx->more.size()) * 16 / std::max<uint32_t>(16, max_occ));
     return query_file_impl(idx, pattern_path, out, out, batch_bases, stats, false, true, max_occ);
+}
+
+int colbwt_anchors_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t min_len,
+                         uint32_t max_anchors, uint32_t max_occ, colbwt_anchor_summary *summary, uint32_t *anchor_start,
+                         uint32_t *anchor_len, uint64_t *anchor_occ, uint64_t *anchor_pos, colbwt_stats *stats) {
+    return anchors_batch_all(idx, bases, read_off, n_reads, min_len, max_anchors, max_occ, summary, anchor_start, anchor_len,
+                             anchor_occ, anchor_pos, stats);
+}
+
+int colbwt_anchors_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads, uint64_t n_bases,
+                          uint32_t min_len, uint32_t max_anchors, uint32_t max_occ, colbwt_anchor_summary *d_summary,
+                          uint32_t *d_start, uint32_t *d_len, uint64_t *d_occ, uint64_t *d_pos, const uint32_t *d_order,
+                          void *hip_stream, colbwt_stats *stats) {
+    auto bad_argument = [&]() -> const char * {
+        if (const char *m = anchors_bad_setup(idx, min_len, max_anchors, max_occ, d_start, d_len, d_occ, d_pos)) return m;
+        if (n_reads >= 0xFFFFFFFFull) return "more than 2^32-2 reads in a batch";
+        if (n_reads == 0) return nullptr;
+        if (!d_bases || !d_read_off || !d_summary) return "null device pointer";
+        if (((uintptr_t)d_bases & 15) || ((uintptr_t)d_summary & 15) || ((uintptr_t)d_start & 3) || ((uintptr_t)d_len & 3) ||
+            ((uintptr_t)d_occ & 7) || ((uintptr_t)d_pos & 7))
+            return "d_bases/d_summary must be 16-byte aligned, d_start/d_len 4-byte and d_occ/d_pos 8-byte aligned";
+        return nullptr;
+    };
+    return device_entry(idx, d_bases, n_reads, n_bases, hip_stream, 0, stats, bad_argument,
+                        [&](const Index &ix, hipStream_t stream) {
+                            launch_anchors(ix,
+                                           anchors_args(replica_for(idx, d_bases), min_len, max_anchors, max_occ, d_summary, d_start,
+                                                        d_len, d_occ, d_pos),
+                                           d_bases, d_read_off, n_reads, d_order, stream);
+                        });
+}
+
+int colbwt_anchors_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t min_len, uint32_t max_anchors,
+                        uint32_t max_occ, uint64_t batch_bases, colbwt_stats *stats) {
+    if (!idx || !pattern_path) return fail(COLBWT_ERR_ARG, "null argument");
+    if (const char *m = anchors_bad_params(min_len, max_anchors, max_occ)) return fail(COLBWT_ERR_ARG, m);
+    if (max_occ > 0 && !idx->loc.ready()) return fail(COLBWT_ERR_ARG, "no locate samples attached (colbwt_index_attach_locate)");
+    const std::string out = out_path ? out_path : std::string(pattern_path) + ".anchors";
+    if (batch_bases == 0) {   // the default batch of the file query, cut by the slot bytes per read as locate cuts it by max_occ
+        const uint64_t slot_bytes = (uint64_t)max_anchors * (16 + 8 * (uint64_t)max_occ);
+        batch_bases = std::max<uint64_t>(1ull << 20, (64ull << 20) * (1 + idx->more.size()) * 128 / std::max<uint64_t>(128, slot_bytes));
+    }
+    return query_file_impl(idx, pattern_path, out, out, batch_bases, stats, false, true, 0, 0, 0, 0, 0, min_len, max_anchors, max_occ);
 }
 
 uint32_t colbwt_locate_all_tile(void) { return kLocAllTile; }

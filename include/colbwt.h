@@ -337,6 +337,82 @@ int colbwt_locate_all_batch(colbwt_index *idx, const uint8_t *bases, const uint6
 int colbwt_locate_all_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t min_len, uint64_t max_per_read,
                            uint64_t batch_bases, colbwt_stats *stats);
 
+/* ---- anchors: left-maximal exact matches along the whole read --------------------------------
+ * colbwt_count_* / colbwt_locate_* answer for one stretch of the read, its longest matching suffix.
+ * Here the search restarts instead of ending: the anchors of read P[0..m) are the greedy right-to-left
+ * factorisation of the read against the text, defined through the search colbwt_locate_* specifies.
+ * Parameters min_len >= 1, max_anchors in 1 .. 2^16, max_occ in 0 .. 2^20.
+ *   e = m - 1
+ *   while e >= 0:
+ *     (L, occ, [sp, ep]) = locate's search on the prefix P[0..e]: the longest suffix of P[0..e] that
+ *                          occurs; a byte <= 1 or a character absent from the table ends it
+ *     if L == 0:  skipped += 1; e -= 1                    (this base lies in no match)
+ *     else:       factor (start = e - L + 1, len = L, occ, positions SA[ep], SA[ep-1], ..); e -= L
+ *   left-maximal  a factor cannot be extended to the left: the base in front of it is the one that
+ *            failed, or the read starts there.  The base that failed is the last base of the next
+ *            factor: it is retried from the full range, not dropped.
+ *   progress on a synthetic table the full-range retry of a present character may still come back empty
+ *            (sp > ep after LF): that is L == 0 and the base is skipped, so the loop advances on every
+ *            validated table.
+ *   factor 0 when colbwt_locate_* reports mlen > 0 for the read, factor 0 is locate's answer:
+ *            start = m - mlen, and len, occ and the first min(occ, max_occ) positions in the same order.
+ *   bound    the greedy parse is the partition of the non-skipped bases into the FEWEST substrings of
+ *            the text (each greedy factor reaches at least as far left as any other parse's factor
+ *            that ends at or right of the same base).  A read within d substitutions of a text substring
+ *            splits into at most d + 1 substrings of the text and d single bases, each of which is a
+ *            factor or skipped, so n_factors + skipped <= 2d + 1: n_factors is a lower bound on mismatches.
+ *   summary  colbwt_anchor_summary, eight u32, written for every read:
+ *     n_factors   all factors (len >= 1)
+ *     max_len     longest factor, whatever min_len is
+ *     skipped     bases in no factor; sum(len over all factors) + skipped == m
+ *     n_kept      factors with len >= min_len: the anchors
+ *     cov         sum of len over anchors; with min_len == 1, cov + skipped == m
+ *     n_unique    anchors with occ == 1
+ *     cov_unique  sum of len over anchors with occ == 1
+ *     n_stored    min(n_kept, max_anchors)
+ *   slots    a read's anchors in computation order -- largest start first, the order of the binary
+ *            containers and of seeds; the first n_stored fill the read's max_anchors slots: read k owns
+ *            [k * max_anchors, (k+1) * max_anchors) of anchor_start (u32), anchor_len (u32), anchor_occ
+ *            (u64), and slot s owns anchor_pos[s * max_occ, (s+1) * max_occ) (u64): SA[ep], SA[ep-1], ..,
+ *            the first min(occ, max_occ) in locate's order.  Unused slots hold COLBWT_ANCHOR_NONE, 0 and
+ *            0; every position entry past min(occ, max_occ), in used and unused slots alike, holds
+ *            COLBWT_LOCATE_NONE.  Factors shorter than min_len are counted in the summary and never walked.
+ *   max_occ == 0  no positions are produced, anchor_pos is NULL and the mode needs NO locate samples;
+ *            every other output is identical with and without samples.  With max_occ >= 1 samples must
+ *            be attached ("no locate samples attached" is COLBWT_ERR_ARG, as for locate).
+ * The output is deterministic: every slot has one writer and no atomics are involved.  There are no
+ * per-base arrays: the per-base restart-at-zero matching length is a function of the factors (e - k + 1
+ * at base k of a factor whose last base is e, 0 on a skipped base).  Interior factors are left-maximal but
+ * not necessarily right-maximal, so these are NOT super-maximal exact matches.
+ *
+ * colbwt_anchors_device: arguments, stream, stats, d_order and the concurrency contract as
+ * colbwt_locate_device; it allocates nothing and initialises every slot itself.  d_bases 16-byte aligned
+ * with 64 readable bytes past read_off[n_reads], d_summary 16-byte, d_start / d_len 4-byte, d_occ / d_pos
+ * 8-byte aligned.  d_start, d_len and d_occ may all be NULL together (summaries only; d_pos NULL too);
+ * d_pos must be non-NULL exactly when the slots are given and max_occ > 0.  Fewer than 2^32-1 reads per
+ * call, reads up to 2^32-1 bases.
+ * colbwt_anchors_batch: reads in host memory, sharded over the replicas as colbwt_locate_batch shards
+ * them; the same rule for the slot pointers.
+ * colbwt_anchors_file: FASTA/FASTQ(.gz) in (the reader and batch pipeline of colbwt_locate_file), one
+ * line per read "name\tm\tn_factors\tn_kept\tcov\tmax_len\tskipped\tn_unique\tcov_unique\tA,A,..\n", A =
+ * "start:len:occ" followed by "@doc:offset" for each stored position (doc and offset as
+ * colbwt_locate_file prints them), e.g. "120:30:2@0:1543@3:88,95:24:1@1:7"; the last field is empty when
+ * nothing is stored; out_path NULL => pattern + ".anchors"; batch_bases 0 is colbwt_query_file's default,
+ * cut by the slot bytes per read as colbwt_locate_file cuts it by max_occ. */
+#define COLBWT_ANCHOR_NONE 0xFFFFFFFFu
+typedef struct colbwt_anchor_summary {
+    uint32_t n_factors, max_len, skipped, n_kept, cov, n_unique, cov_unique, n_stored;
+} colbwt_anchor_summary;
+int colbwt_anchors_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads, uint64_t n_bases,
+                          uint32_t min_len, uint32_t max_anchors, uint32_t max_occ, colbwt_anchor_summary *d_summary,
+                          uint32_t *d_start, uint32_t *d_len, uint64_t *d_occ, uint64_t *d_pos, const uint32_t *d_order,
+                          void *hip_stream, colbwt_stats *stats);
+int colbwt_anchors_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t min_len,
+                         uint32_t max_anchors, uint32_t max_occ, colbwt_anchor_summary *summary, uint32_t *anchor_start,
+                         uint32_t *anchor_len, uint64_t *anchor_occ, uint64_t *anchor_pos, colbwt_stats *stats);
+int colbwt_anchors_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t min_len, uint32_t max_anchors,
+                        uint32_t max_occ, uint64_t batch_bases, colbwt_stats *stats);
+
 /* ---- seeds: per-read PML peaks and chain summaries, reduced on the device -----------------
  * What read classification consumes of a query's output, so that tens of bytes per read leave the
  * device instead of 3 bytes per base.  The reference has no such mode; these semantics are this
