@@ -39,6 +39,7 @@ EXPORTS = (
     "colbwt_locate_all_tile", "colbwt_locate_all_work_bytes", "colbwt_locate_all_plan_device", "colbwt_locate_all_fill_device",
     "colbwt_locate_all_batch", "colbwt_locate_all_file",
     "colbwt_anchors_device", "colbwt_anchors_batch", "colbwt_anchors_file",
+    "colbwt_chain_work_bytes", "colbwt_chain_reduce_device", "colbwt_chain_device", "colbwt_chain_batch", "colbwt_chain_file",
 )
 
 SEED_NONE = 0xFFFFFFFF          # include/colbwt.h COLBWT_SEED_NONE: seed_pos of a slot past the read's min(n_seeds, max_seeds)
@@ -49,6 +50,9 @@ ANCHOR_NONE = 0xFFFFFFFF        # include/colbwt.h COLBWT_ANCHOR_NONE: anchor_st
 # colbwt_anchor_summary as a numpy record: one per read
 AnchorSummary = np.dtype([(k, np.uint32) for k in ("n_factors", "max_len", "skipped", "n_kept", "cov", "n_unique", "cov_unique",
                                                    "n_stored")])
+# colbwt_chain as a numpy record: one per read, 32 bytes; text_begin is LOCATE_NONE (and the rest 0) for a read without hits
+CHAIN = np.dtype([("text_begin", np.uint64), ("text_len", np.uint32), ("read_begin", np.uint32), ("read_end", np.uint32),
+                  ("score", np.uint32), ("score2", np.uint32), ("n_chained", np.uint16), ("n_hits", np.uint16)])
 
 
 class ColbwtError(RuntimeError):
@@ -160,6 +164,12 @@ def lib():
     L.colbwt_anchors_device.argtypes = [vp, vp, vp, u64, u64, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(Stats)]
     L.colbwt_anchors_batch.argtypes = [vp, vp, vp, u64, u32, u32, u32, vp, vp, vp, vp, vp, C.POINTER(Stats)]
     L.colbwt_anchors_file.argtypes = [vp, C.c_char_p, C.c_char_p, u32, u32, u32, u64, C.POINTER(Stats)]
+    L.colbwt_chain_work_bytes.argtypes = [u64, u32, u32]
+    L.colbwt_chain_work_bytes.restype = u64
+    L.colbwt_chain_reduce_device.argtypes = [vp, vp, vp, vp, u64, u32, u32, u32, vp, vp, C.POINTER(Stats)]
+    L.colbwt_chain_device.argtypes = [vp, vp, vp, u64, u64, u32, u32, u32, u32, vp, vp, vp, vp, C.POINTER(Stats)]
+    L.colbwt_chain_batch.argtypes = [vp, vp, vp, u64, u32, u32, u32, u32, vp, C.POINTER(Stats)]
+    L.colbwt_chain_file.argtypes = [vp, C.c_char_p, C.c_char_p, u32, u32, u32, u32, u64, C.POINTER(Stats)]
     _lib = L
     return L
 
@@ -512,6 +522,51 @@ class ColPml:
                                          int(min_len), int(max_anchors), int(max_occ), batch_bases, C.byref(st)))
         return st
 
+    # -- chain: the best colinear chain of each read's anchors (include/colbwt.h colbwt_chain_*) --
+    def chain_batch(self, bases, read_off, min_len=16, max_anchors=16, max_occ=4, band=16):
+        """Many reads -> (chain, Stats): a CHAIN record per read; the anchors stay on the device."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        read_off = np.ascontiguousarray(read_off, dtype=np.uint64)
+        n_reads = max(read_off.size - 1, 0)
+        chain = np.zeros(n_reads, CHAIN)
+        st = Stats()
+        _check(lib().colbwt_chain_batch(self._h, bases.ctypes.data, read_off.ctypes.data, n_reads, int(min_len), int(max_anchors),
+                                        int(max_occ), int(band), chain.ctypes.data, C.byref(st)))
+        return chain, st
+
+    def chain(self, pattern, min_len=16, max_anchors=16, max_occ=4, band=16):
+        """One read -> its chain as a dict of the CHAIN fields, or None when no anchor has a position."""
+        p = np.frombuffer(bytes(pattern), dtype=np.uint8)
+        chain, _ = self.chain_batch(p, np.array([0, p.size], np.uint64), min_len, max_anchors, max_occ, band)
+        if int(chain["text_begin"][0]) == LOCATE_NONE:
+            return None
+        return {f: int(chain[f][0]) for f in CHAIN.names}
+
+    def chain_reduce_device(self, d_start, d_len, d_pos, n_reads, max_anchors, max_occ, band, d_chain, stream=0, timed=False):
+        """The reduction alone over device arrays of the shape anchors_device fills: raw device pointers (ints);
+        d_chain n_reads CHAIN records, 16-byte aligned."""
+        st = Stats()
+        _check(lib().colbwt_chain_reduce_device(self._h, d_start, d_len, d_pos, n_reads, int(max_anchors), int(max_occ), int(band),
+                                                d_chain, stream, C.byref(st) if timed else None))
+        return st
+
+    def chain_device(self, d_bases, d_read_off, n_reads, n_bases, min_len, max_anchors, max_occ, band, d_chain, d_work, d_order=None,
+                     stream=0, timed=False):
+        """Device-resident chain entry point: anchors into d_work (chain_work_bytes(n_reads, max_anchors, max_occ) bytes,
+        256-byte aligned), then the reduction into d_chain."""
+        st = Stats()
+        _check(lib().colbwt_chain_device(self._h, d_bases, d_read_off, n_reads, n_bases, int(min_len), int(max_anchors), int(max_occ),
+                                         int(band), d_chain, d_work, d_order, stream, C.byref(st) if timed else None))
+        return st
+
+    def chain_file(self, pattern_path, out_path=None, min_len=16, max_anchors=16, max_occ=4, band=16, batch_bases=0):
+        """FASTA/FASTQ(.gz) -> text lines "name\tm\tread_begin\tread_end\tdoc\toffset\ttext_len\tscore\tscore2\tn_chained\tn_hits"
+        (default <pattern>.chains); doc and offset are "*" for a read without a chain."""
+        st = Stats()
+        _check(lib().colbwt_chain_file(self._h, os.fsencode(pattern_path), os.fsencode(out_path) if out_path else None,
+                                       int(min_len), int(max_anchors), int(max_occ), int(band), batch_bases, C.byref(st)))
+        return st
+
     # -- docs: the documents holding each read's longest exact match (include/colbwt.h colbwt_docs_*) --
     def docs_mask_words(self):
         """W = ceil(n_docs / 64): u64 mask words per read (0 when no locate samples are attached)."""
@@ -604,6 +659,11 @@ def docs_work_bytes(n_reads):
 def locate_all_work_bytes(n_reads):
     """colbwt_locate_all_work_bytes: size of the device workspace a locate-all plan over n_reads reads needs."""
     return int(lib().colbwt_locate_all_work_bytes(int(n_reads)))
+
+
+def chain_work_bytes(n_reads, max_anchors, max_occ):
+    """colbwt_chain_work_bytes: size of the device scratch a chain_device call keeps its anchors in."""
+    return int(lib().colbwt_chain_work_bytes(int(n_reads), int(max_anchors), int(max_occ)))
 
 
 def _mask_docs(mask_row):

@@ -23,6 +23,7 @@
 #include "../../include/colbwt.h"
 #include "anchors_query.h"
 #include "bin_writer.h"
+#include "chain_reduce.h"
 #include "count_query.h"
 #include "docs_query.h"
 #include "fasta_parallel.h"
@@ -722,6 +723,95 @@ const char *docs_bad_params(uint32_t min_len, uint32_t max_walk) {
     return nullptr;
 }
 
+const char *chain_bad_params(uint32_t max_anchors, uint32_t max_occ) {
+    if (max_anchors == 0) return "max_anchors must be at least 1";
+    if (max_occ == 0) return "max_occ must be at least 1";
+    if ((uint64_t)max_anchors * max_occ > kChainMaxHits) return "max_anchors * max_occ must be at most 256";
+    return nullptr;
+}
+
+// The chain parameters, then the samples of every replica and their document count.
+const char *chain_bad_setup(const colbwt_index *idx, uint32_t max_anchors, uint32_t max_occ) {
+    if (const char *m = chain_bad_params(max_anchors, max_occ)) return m;
+    if (!idx->loc.ready()) return "no locate samples attached (colbwt_index_attach_locate)";
+    for (const colbwt_index *r : idx->more)
+        if (!r->loc.ready()) return "no locate samples attached (colbwt_index_attach_locate)";
+    if (idx->loc.n_docs() > kDocsLds) return kDocsTooMany;
+    return nullptr;
+}
+
+ChainArgs chain_args(const colbwt_index *rep, const uint32_t *start, const uint32_t *len, const uint64_t *pos, uint32_t max_anchors,
+                     uint32_t max_occ, uint32_t band, void *chain) {
+    return ChainArgs{start, len, pos, rep->loc.doc_dev.as<const uint32_t>(), rep->loc.n_docs(), max_anchors, max_occ, band, (uint4 *)chain};
+}
+
+// The anchors' arrays of a chain call, cut from a 256-byte aligned scratch of chain_work_bytes() bytes.
+struct ChainWork {
+    colbwt_anchor_summary *summary;
+    uint32_t *start, *len;
+    uint64_t *occ, *pos;
+};
+uint64_t chain_work_bytes(uint64_t n_reads, uint32_t max_anchors, uint32_t max_occ) {
+    const uint64_t slots = n_reads * max_anchors;
+    return docs_align(32 * n_reads) + 2 * docs_align(4 * slots) + docs_align(8 * slots) + docs_align(8 * slots * max_occ);
+}
+ChainWork chain_work(void *d_work, uint64_t n_reads, uint32_t max_anchors, uint32_t max_occ) {
+    const uint64_t slots = n_reads * max_anchors;
+    uint8_t *p = (uint8_t *)d_work;
+    ChainWork w;
+    w.summary = (colbwt_anchor_summary *)p;
+    p += docs_align(32 * n_reads);
+    w.start = (uint32_t *)p;
+    p += docs_align(4 * slots);
+    w.len = (uint32_t *)p;
+    p += docs_align(4 * slots);
+    w.occ = (uint64_t *)p;
+    p += docs_align(8 * slots);
+    w.pos = (uint64_t *)p;
+    return w;
+}
+
+// Anchors into `d_work`, then the reduction (chain_reduce.h), back to back on one stream.
+hipError_t launch_chain_of_reads(const colbwt_index *rep, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads,
+                                 uint32_t min_len, uint32_t max_anchors, uint32_t max_occ, uint32_t band, void *d_chain, void *d_work,
+                                 const uint32_t *d_order, hipStream_t stream) {
+    const ChainWork w = chain_work(d_work, n_reads, max_anchors, max_occ);
+    launch_anchors(rep->ix, anchors_args(rep, min_len, max_anchors, max_occ, w.summary, w.start, w.len, w.occ, w.pos), d_bases, d_read_off,
+                   n_reads, d_order, stream);
+    return launch_chain(chain_args(rep, w.start, w.len, w.pos, max_anchors, max_occ, band, d_chain), n_reads, stream);
+}
+
+// Chains for a batch in host memory: the first result array of the scratch holds the records, the second
+// the anchors' arrays, which never leave HBM.
+int chain_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t min_len,
+                    uint32_t max_anchors, uint32_t max_occ, uint32_t band, colbwt_chain *chain, colbwt_stats *stats) {
+    if (idx) {
+        if (min_len == 0) return fail(COLBWT_ERR_ARG, "min_len must be at least 1");
+        if (const char *m = chain_bad_setup(idx, max_anchors, max_occ)) return fail(COLBWT_ERR_ARG, m);
+        if (n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, "more than 2^32-2 reads in a batch");
+    }
+    auto bad_pointers = [&](uint64_t n_bases) -> const char * { return (n_bases && !bases) || !chain ? "null bases/chain" : nullptr; };
+    auto part = [&](colbwt_index *rep, uint64_t lo, uint64_t hi, uint64_t max_len, uint64_t min_read, colbwt_stats *st,
+                    std::string &msg) {
+        const uint64_t n = hi - lo, off0 = read_off[lo];
+        const uint64_t out_bytes[2] = {n * sizeof(colbwt_chain), chain_work_bytes(n, max_anchors, max_occ)};
+        hipError_t launched = hipSuccess;
+        auto launch = [&](const DeviceBatch &b) {
+            launched = launch_chain_of_reads(rep, b.bases, b.off, n, min_len, max_anchors, max_occ, band, b.out[0], b.out[1], b.order,
+                                             b.stream);
+        };
+        auto fetch = [&](const DeviceBatch &b) {
+            TRY_HIP(launched, b.stream, msg);
+            TRY_HIP(hipMemcpyAsync(chain + lo, b.out[0], n * sizeof(colbwt_chain), hipMemcpyDeviceToHost, b.stream), b.stream, msg);
+            return COLBWT_OK;
+        };
+        return replica_batch(rep, bases + off0, read_off + lo, off0, n, max_len, min_read, true, out_bytes, 0, st, msg, launch,
+                             fetch);
+    };
+    return sharded_batch(idx, read_off, n_reads, 0xFFFFFFFFull, "read longer than 2^32-1 bases", true, stats, bad_pointers,
+                         part);
+}
+
 // Docs (docs_query.h) for a batch in host memory: search, order, walk and tally run back to back on
 // the replica's stream; positions never leave HBM.  The first result array of the scratch holds mlen,
 // then n_hit; the second the workspace, occ, the masks and the shard's two tallies, which are summed
@@ -1379,12 +1469,13 @@ int colbwt_query_device_ordered(colbwt_index *idx, const uint8_t *d_bases, const
 // (with `count`): docs (docs_query.h) with min_len = docs_min and max_walk = docs_w, one line per read
 // and, after the last batch, pml_name + ".tally", as colbwt_docs_file documents them.  `anch_k` > 0 (with
 // `count`): anchors (anchors_query.h) with min_len = anch_min, max_anchors = anch_k and max_occ = anch_occ,
-// one line per read as colbwt_anchors_file documents it.
+// one line per read as colbwt_anchors_file documents it; with `chain` the anchors are reduced on the device
+// (chain_reduce.h, band = chain_band) and the lines are those of colbwt_chain_file.
 static int query_file_impl(colbwt_index *idx, const char *pattern_path, const std::string &pml_name,
                            const std::string &cid_name, uint64_t batch_bases, colbwt_stats *stats, bool binary,
                            bool count = false, uint32_t locate_k = 0, uint32_t seeds_min = 0, uint32_t seeds_k = 0,
                            uint32_t docs_min = 0, uint32_t docs_w = 0, uint32_t anch_min = 0, uint32_t anch_k = 0,
-                           uint32_t anch_occ = 0) {
+                           uint32_t anch_occ = 0, bool chain = false, uint32_t chain_band = 0) {
     if (stats) memset(stats, 0, sizeof(*stats));
     const uint32_t docs_n = docs_w ? idx->loc.n_docs() : 0, docs_words = docs_mask_words(docs_n);
     std::vector<uint64_t> docs_tally(2 * (size_t)docs_n, 0), docs_part(2 * (size_t)docs_n, 0);   // doc_reads, then doc_only
@@ -1494,6 +1585,26 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
                 free_q.push(b);
                 continue;
             }
+            if (chain) {
+                const colbwt_chain *ch = b->pml->as<colbwt_chain>();
+                const std::vector<uint64_t> &ds = idx->loc.doc_start;
+                for (uint64_t k = 0; k < n_reads && count_ok; ++k) {
+                    const colbwt_chain &c = ch[k];
+                    count_ok = fprintf(wn, "%s\t%llu\t%u\t%u\t", b->names[k].c_str(), (unsigned long long)(b->off[k + 1] - b->off[k]),
+                                       c.read_begin, c.read_end) > 0;
+                    if (c.text_begin == COLBWT_LOCATE_NONE) {
+                        count_ok = count_ok && fputs("*\t*", wn) != EOF;
+                    } else {
+                        const size_t d = (size_t)(std::upper_bound(ds.begin(), ds.end(), c.text_begin) - ds.begin()) - 1;
+                        count_ok = count_ok && fprintf(wn, "%zu\t%llu", d, (unsigned long long)(c.text_begin - ds[d])) > 0;
+                    }
+                    count_ok = count_ok && fprintf(wn, "\t%u\t%u\t%u\t%u\t%u\n", c.text_len, c.score, c.score2, (unsigned)c.n_chained,
+                                                   (unsigned)c.n_hits) > 0;
+                }
+                t_format += now() - t0;
+                free_q.push(b);
+                continue;
+            }
             if (anch_k) {
                 const uint32_t *sm = b->pml->as<uint32_t>();           // 8 words per read
                 const uint32_t *as = sm + 8 * n_reads, *al = as + n_reads * anch_k;
@@ -1592,7 +1703,9 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
             rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
         if (rc == COLBWT_OK && docs_w && (!b->pml->ensure(n_reads * 8) || !b->cid->ensure(n_reads * 8 * (1 + (uint64_t)docs_words))))
             rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
-        if (rc == COLBWT_OK && anch_k &&
+        if (rc == COLBWT_OK && chain && !b->pml->ensure(n_reads * sizeof(colbwt_chain)))
+            rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
+        if (rc == COLBWT_OK && anch_k && !chain &&
             (!b->pml->ensure(n_reads * (32 + 8 * (uint64_t)anch_k)) || !b->cid->ensure(n_reads * anch_k * 8 * (1 + (uint64_t)anch_occ))))
             rc = fail(COLBWT_ERR_NOMEM, "cannot pin host memory for a batch of results");
         if (rc == COLBWT_OK && count && !seeds_k && !docs_w && !anch_k && (!b->pml->ensure(n_reads * 4) || !b->cid->ensure(n_reads * 8 * (1 + (uint64_t)locate_k))))
@@ -1604,6 +1717,9 @@ static int query_file_impl(colbwt_index *idx, const char *pattern_path, const st
             uint32_t *sp = b->cid->as<uint32_t>(), *sl = sp + n_reads * seeds_k;
             rc = seeds_batch_all(idx, b->bases.data(), b->off.data(), n_reads, seeds_min, seeds_k, b->pml->as<uint32_t>(), sp, sl,
                                  (uint8_t *)(sl + n_reads * seeds_k), &st);
+        } else if (chain) {
+            rc = chain_batch_all(idx, b->bases.data(), b->off.data(), n_reads, anch_min, anch_k, anch_occ, chain_band,
+                                 b->pml->as<colbwt_chain>(), &st);
         } else if (anch_k) {
             uint32_t *as = b->pml->as<uint32_t>() + 8 * n_reads;
             uint64_t *ao = b->cid->as<uint64_t>();
@@ -1902,6 +2018,72 @@ int colbwt_anchors_file(colbwt_index *idx, const char *pattern_path, const char 
         batch_bases = std::max<uint64_t>(1ull << 20, (64ull << 20) * (1 + idx->more.size()) * 128 / std::max<uint64_t>(128, slot_bytes));
     }
     return query_file_impl(idx, pattern_path, out, out, batch_bases, stats, false, true, 0, 0, 0, 0, 0, min_len, max_anchors, max_occ);
+}
+
+uint64_t colbwt_chain_work_bytes(uint64_t n_reads, uint32_t max_anchors, uint32_t max_occ) {
+    return chain_work_bytes(n_reads, max_anchors, max_occ);
+}
+
+int colbwt_chain_reduce_device(colbwt_index *idx, const uint32_t *d_start, const uint32_t *d_len, const uint64_t *d_pos,
+                               uint64_t n_reads, uint32_t max_anchors, uint32_t max_occ, uint32_t band, colbwt_chain *d_chain,
+                               void *hip_stream, colbwt_stats *stats) {
+    auto bad_argument = [&]() -> const char * {
+        if (const char *m = chain_bad_setup(idx, max_anchors, max_occ)) return m;
+        if (n_reads >= 0xFFFFFFFFull) return "more than 2^32-2 reads in a batch";
+        if (n_reads == 0) return nullptr;
+        if (!d_start || !d_len || !d_pos || !d_chain) return "null device pointer";
+        if (((uintptr_t)d_start & 3) || ((uintptr_t)d_len & 3) || ((uintptr_t)d_pos & 7) || ((uintptr_t)d_chain & 15))
+            return "d_start/d_len must be 4-byte aligned, d_pos 8-byte and d_chain 16-byte aligned";
+        return nullptr;
+    };
+    hipError_t launched = hipSuccess;
+    const int rc = device_entry(idx, d_pos, n_reads, 0, hip_stream, 0, stats, bad_argument, [&](const Index &, hipStream_t stream) {
+        launched = launch_chain(chain_args(replica_for(idx, d_pos), d_start, d_len, d_pos, max_anchors, max_occ, band, d_chain), n_reads,
+                                stream);
+    });
+    if (rc == COLBWT_OK && launched != hipSuccess) return hip_failed(launched, "colbwt_chain_reduce_device", nullptr, g_err);
+    return rc;
+}
+
+int colbwt_chain_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads, uint64_t n_bases,
+                        uint32_t min_len, uint32_t max_anchors, uint32_t max_occ, uint32_t band, colbwt_chain *d_chain, void *d_work,
+                        const uint32_t *d_order, void *hip_stream, colbwt_stats *stats) {
+    auto bad_argument = [&]() -> const char * {
+        if (min_len == 0) return "min_len must be at least 1";
+        if (const char *m = chain_bad_setup(idx, max_anchors, max_occ)) return m;
+        if (n_reads >= 0xFFFFFFFFull) return "more than 2^32-2 reads in a batch";
+        if (n_reads == 0) return nullptr;
+        if (!d_bases || !d_read_off || !d_chain || !d_work) return "null device pointer";
+        if (((uintptr_t)d_bases & 15) || ((uintptr_t)d_chain & 15)) return "d_bases/d_chain must be 16-byte aligned";
+        if ((uintptr_t)d_work & 255) return "d_work must be 256-byte aligned";
+        return nullptr;
+    };
+    hipError_t launched = hipSuccess;
+    const int rc = device_entry(idx, d_bases, n_reads, n_bases, hip_stream, 0, stats, bad_argument, [&](const Index &, hipStream_t stream) {
+        launched = launch_chain_of_reads(replica_for(idx, d_bases), d_bases, d_read_off, n_reads, min_len, max_anchors, max_occ, band,
+                                         d_chain, d_work, d_order, stream);
+    });
+    if (rc == COLBWT_OK && launched != hipSuccess) return hip_failed(launched, "colbwt_chain_device", nullptr, g_err);
+    return rc;
+}
+
+int colbwt_chain_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t min_len,
+                       uint32_t max_anchors, uint32_t max_occ, uint32_t band, colbwt_chain *chain, colbwt_stats *stats) {
+    return chain_batch_all(idx, bases, read_off, n_reads, min_len, max_anchors, max_occ, band, chain, stats);
+}
+
+int colbwt_chain_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t min_len, uint32_t max_anchors,
+                      uint32_t max_occ, uint32_t band, uint64_t batch_bases, colbwt_stats *stats) {
+    if (!idx || !pattern_path) return fail(COLBWT_ERR_ARG, "null argument");
+    if (min_len == 0) return fail(COLBWT_ERR_ARG, "min_len must be at least 1");
+    if (const char *m = chain_bad_setup(idx, max_anchors, max_occ)) return fail(COLBWT_ERR_ARG, m);
+    const std::string out = out_path ? out_path : std::string(pattern_path) + ".chains";
+    if (batch_bases == 0) {   // colbwt_anchors_file's default: the slot bytes per read stay in HBM but still set the scratch
+        const uint64_t slot_bytes = (uint64_t)max_anchors * (16 + 8 * (uint64_t)max_occ);
+        batch_bases = std::max<uint64_t>(1ull << 20, (64ull << 20) * (1 + idx->more.size()) * 128 / std::max<uint64_t>(128, slot_bytes));
+    }
+    return query_file_impl(idx, pattern_path, out, out, batch_bases, stats, false, true, 0, 0, 0, 0, 0, min_len, max_anchors, max_occ, true,
+                           band);
 }
 
 uint32_t colbwt_locate_all_tile(void) { return kLocAllTile; }

@@ -413,6 +413,76 @@ int colbwt_anchors_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t
 int colbwt_anchors_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t min_len, uint32_t max_anchors,
                         uint32_t max_occ, uint64_t batch_bases, colbwt_stats *stats);
 
+/* ---- chain: the best colinear chain of each read's anchors, reduced on the device ------------
+ * colbwt_anchors_* says which stretches of a read occur and where; this joins them: one locus per
+ * read with a score and a runner-up, 32 bytes per read instead of the slot arrays.
+ *   inputs   the slot arrays of colbwt_anchors_* for one read: anchor_start[K], anchor_len[K],
+ *            anchor_pos[K * M], K = max_anchors, M = max_occ >= 1, and a u32 parameter band.  The arrays
+ *            are taken as given: any arrays of that shape do, positions are not validated.
+ *   hits     slot a is USED iff anchor_start[a] != COLBWT_ANCHOR_NONE.  A hit is (a, s = anchor_start[a],
+ *            l = anchor_len[a], t = anchor_pos[a * M + q]) for a used slot and every q < M with
+ *            anchor_pos[a * M + q] != COLBWT_LOCATE_NONE.  Hits are numbered 0 .. H-1 by (a, q) ascending;
+ *            on the output of anchors that is right to left in the read.  doc(t) is the document of t
+ *            under the attached samples' doc_start: the last d with doc_start[d] <= t, the rule of docs.
+ *   transition  hit j may precede hit i iff  j < i and a_j < a_i;  gr = s_j - (s_i + l_i) >= 0;
+ *            gt = t_j - (t_i + l_i) >= 0;  doc(t_i) == doc(t_j);  drift = |gt - gr| <= band.
+ *            gr and gt are signed 64-bit (t_i + l_i and the difference are taken modulo 2^64, then read
+ *            as signed; s_i + l_i does not wrap).
+ *   score    f(i) = l_i + max(0, max over j of (f(j) - drift(j, i))): a predecessor is taken only when
+ *            f(j) - drift > 0, and among equal candidates the smallest j wins.  f is computed in signed
+ *            64-bit and stored saturated to u32 (2^32-1); later hits see the stored value.
+ *   best chain  ends at the hit e with the largest f, the smallest e among equals; following the
+ *            predecessors back leads to its first hit b, the rightmost in the read.
+ *              read_begin = s_e            read_end = s_b + l_b (modulo 2^32)
+ *              text_begin = t_e            text_end = t_b + l_b (modulo 2^64)
+ *              text_len   = text_end - text_begin, saturated to u32
+ *              score = f(e)    n_chained = hits on the path    n_hits = H
+ *   runner-up  score2 is the largest f of the same dynamic program run again over the hits that lie
+ *            outside the best chain's text interval -- t + l <= text_begin or t >= text_end -- in their
+ *            order; 0 when there are none.  It is the best alternative locus: score - score2 is what a
+ *            caller turns into a mapping quality.
+ *   no hits  text_begin = COLBWT_LOCATE_NONE and every other field is 0.
+ *   limits   1 <= max_anchors, 1 <= max_occ, max_anchors * max_occ <= 256; anything else is
+ *            COLBWT_ERR_ARG with a message.  Locate samples must be attached ("no locate samples attached"
+ *            is COLBWT_ERR_ARG, as for locate), with at most 4096 documents, as for docs.
+ *   out of scope  a chain never joins two documents.  Records, and the reverse-complement half, inside one
+ *            document are not told apart, because .col_loc holds no record table: the position is a text
+ *            position, printed as doc:offset the way locate prints it.  No base-level alignment, no
+ *            SAM/PAF, no strand field.
+ * The output is deterministic: every word has one writer and no atomics are involved.
+ *
+ * colbwt_chain_reduce_device: the reduction alone, over device arrays that a colbwt_anchors_device call
+ * filled (or any arrays of that shape): d_start / d_len n_reads * max_anchors u32 (4-byte aligned), d_pos
+ * n_reads * max_anchors * max_occ u64 (8-byte aligned), d_chain n_reads records (16-byte aligned).  Stream,
+ * stats and the concurrency contract as colbwt_anchors_device; the replica is the one on d_pos's device.
+ * It allocates nothing.  Fewer than 2^32-1 reads per call.
+ * colbwt_chain_device: anchors (min_len, max_anchors, max_occ; d_bases, d_read_off, d_order as
+ * colbwt_anchors_device) into the caller's scratch d_work -- colbwt_chain_work_bytes(n_reads, max_anchors,
+ * max_occ) bytes, 256-byte aligned -- then the reduction, on one stream.  The scratch holds the anchors'
+ * summary, start, len, occ and pos arrays, each starting at a multiple of 256 bytes, in that order.
+ * colbwt_chain_batch: reads in host memory, sharded over the replicas as colbwt_anchors_batch shards
+ * them; only the records come back.
+ * colbwt_chain_file: FASTA/FASTQ(.gz) in, one line per read
+ * "name\tm\tread_begin\tread_end\tdoc\toffset\ttext_len\tscore\tscore2\tn_chained\tn_hits\n" (doc and offset of
+ * text_begin as colbwt_locate_file prints them; both "*" when there is no chain); out_path NULL =>
+ * pattern + ".chains"; batch_bases 0 is colbwt_anchors_file's default. */
+typedef struct colbwt_chain {
+    uint64_t text_begin;
+    uint32_t text_len, read_begin, read_end, score, score2;
+    uint16_t n_chained, n_hits;
+} __attribute__((aligned(16))) colbwt_chain;
+uint64_t colbwt_chain_work_bytes(uint64_t n_reads, uint32_t max_anchors, uint32_t max_occ);
+int colbwt_chain_reduce_device(colbwt_index *idx, const uint32_t *d_start, const uint32_t *d_len, const uint64_t *d_pos,
+                               uint64_t n_reads, uint32_t max_anchors, uint32_t max_occ, uint32_t band, colbwt_chain *d_chain,
+                               void *hip_stream, colbwt_stats *stats);
+int colbwt_chain_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads, uint64_t n_bases,
+                        uint32_t min_len, uint32_t max_anchors, uint32_t max_occ, uint32_t band, colbwt_chain *d_chain, void *d_work,
+                        const uint32_t *d_order, void *hip_stream, colbwt_stats *stats);
+int colbwt_chain_batch(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t min_len,
+                       uint32_t max_anchors, uint32_t max_occ, uint32_t band, colbwt_chain *chain, colbwt_stats *stats);
+int colbwt_chain_file(colbwt_index *idx, const char *pattern_path, const char *out_path, uint32_t min_len, uint32_t max_anchors,
+                      uint32_t max_occ, uint32_t band, uint64_t batch_bases, colbwt_stats *stats);
+
 /* ---- seeds: per-read PML peaks and chain summaries, reduced on the device -----------------
  * What read classification consumes of a query's output, so that tens of bytes per read leave the
  * device instead of 3 bytes per base.  The reference has no such mode; these semantics are this
