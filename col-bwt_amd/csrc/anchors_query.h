@@ -12,8 +12,9 @@
 // the row loads of the step stay at the top of a trip, where the wave is converged (lane_io.h); a
 // restart inside a nested loop would run them under a divergent branch instead.
 //
-// The step is count_kernel's / locate_kernel's, restated once as search_step below (kToe: whether the
+// The step is count_query.h's search_step, the one count and locate take too (kToe: whether the
 // toehold is carried; without it no toe_row load happens, so max_occ == 0 needs no locate samples).
+// The loop around it is this kernel's own: count's and locate's longest_suffix has no restart.
 //
 // Slots: read k owns [k * max_anchors, (k+1) * max_anchors) of start / len / occ and max_occ positions
 // per slot.  During the search a kept factor's slot gets start, len, occ and pos[0] = SA[ep]; when the
@@ -31,78 +32,6 @@
 namespace colbwt {
 
 constexpr uint32_t kAnchorNone = 0xFFFFFFFFu;   // start of a slot past the read's n_stored
-
-// The (row, offset) cursors of [sp, ep] with the rows they lie in, and toe = SA[ep].
-template <class V>
-struct SearchRange {
-    using Row = typename V::Row;
-    uint32_t js, je;
-    uint64_t os, oe;
-    Row ws, we;
-    uint32_t toe;
-    // [0, n - 1]: row 0 offset 0 .. the last row at its last offset
-    template <bool kToe>
-    __device__ __forceinline__ void full(const V &view, const uint32_t *__restrict__ toe_row) {
-        js = 0;
-        je = view.rows() - 1;
-        ws = view.load(js);
-        we = view.load(je);
-        os = 0;
-        oe = view.len(je, we) - 1;
-        toe = 0;
-        if constexpr (kToe) toe = toe_row[je];   // SA[n - 1]
-    }
-};
-
-// One backward-search step with character c (cidx = its column of the jump tables): the step of
-// count_kernel, and with kToe that of locate_kernel.  True: R is the range of c + (what R matched).
-// False: no such range (c does not occur in R, or LF left an empty range); R is unchanged.
-template <bool kToe, class V>
-__device__ __forceinline__ bool search_step(const V &view, const uint32_t *__restrict__ toe_row, uint32_t c, uint32_t cidx,
-                                            SearchRange<V> &R) {
-    using Row = typename V::Row;
-    uint32_t sj = R.js;
-    uint64_t so = R.os;
-    Row sw = R.ws;
-    if (view.ch(R.ws) != c) {
-        sj = view.succ(R.js, c, cidx, sw);
-        if (sj == kNone) return false;
-        so = 0;
-    }
-    uint32_t ej = R.je;
-    uint64_t eo = R.oe;
-    Row ew = R.we;
-    uint32_t te = R.toe;                 // SA[e]
-    if (view.ch(R.we) != c) {
-        ej = view.pred(R.je, c, cidx, ew);
-        if (ej == kNone) return false;
-        eo = view.len(ej, ew) - 1;
-        if constexpr (kToe) te = toe_row[ej];
-    }
-    if (sj > ej || (sj == ej && so > eo)) return false;
-    uint32_t nj = view.lf_row(sw);
-    uint64_t nt = (uint64_t)view.lf_off(sw) + so;
-    Row nw = view.load(nj);
-    count_fast_forward(view, nj, nt, nw);
-    uint32_t mj;
-    uint64_t mt;
-    Row mw;
-    if (sj == ej) {                      // one row: the image of [so, eo] is contiguous
-        mj = nj;
-        mt = nt + (eo - so);
-        mw = nw;
-    } else {
-        mj = view.lf_row(ew);
-        mt = (uint64_t)view.lf_off(ew) + eo;
-        mw = view.load(mj);
-    }
-    count_fast_forward(view, mj, mt, mw);
-    if (nj > mj || (nj == mj && nt > mt)) return false;   // empty range: only on synthetic tables
-    R.js = nj; R.os = nt; R.ws = nw;
-    R.je = mj; R.oe = mt; R.we = mw;
-    R.toe = te - 1;
-    return true;
-}
 
 struct AnchorsArgs {
     const uint32_t *toe_row;   // kPos only
@@ -205,28 +134,18 @@ __global__ __launch_bounds__(kQueryBlock) void anchors_kernel(V view, AnchorsArg
     }
 }
 
-template <typename View>
-inline void launch_anchors_view(const View &view, const AnchorsArgs &A, const uint8_t *d_bases, const uint64_t *d_read_off,
-                                uint64_t n_reads, const uint32_t *d_order, hipStream_t stream) {
-    const dim3 grid((uint32_t)((n_reads + kQueryBlock - 1) / kQueryBlock)), block(kQueryBlock);
-    if (A.pos)
-        hipLaunchKernelGGL((anchors_kernel<View, true>), grid, block, 0, stream, view, A, d_bases, d_read_off, n_reads, d_order);
-    else
-        hipLaunchKernelGGL((anchors_kernel<View, false>), grid, block, 0, stream, view, A, d_bases, d_read_off, n_reads, d_order);
-}
-
 // Anchors over whatever layout the index holds.  A.pos non-null: A.toe_row / A.phi were built for that layout.
 inline void launch_anchors(const Index &ix, const AnchorsArgs &A, const uint8_t *d_bases, const uint64_t *d_read_off,
                            uint64_t n_reads, const uint32_t *d_order, hipStream_t stream) {
     if (n_reads == 0) return;
-    if (ix.line_rows())
-        launch_anchors_view(CountFatView{ix.table_fat()}, A, d_bases, d_read_off, n_reads, d_order, stream);
-    else if (ix.layout() == 3)
-        launch_anchors_view(CountSKView<3>{ix.table_k()}, A, d_bases, d_read_off, n_reads, d_order, stream);
-    else if (ix.layout() == 2)
-        launch_anchors_view(CountSKView<2>{ix.table_k()}, A, d_bases, d_read_off, n_reads, d_order, stream);
-    else
-        launch_anchors_view(CountOneStepView{ix.table()}, A, d_bases, d_read_off, n_reads, d_order, stream);
+    with_view(ix, [&](auto view) {
+        using View = decltype(view);
+        const dim3 grid = read_grid(n_reads), block(kQueryBlock);
+        if (A.pos)
+            hipLaunchKernelGGL((anchors_kernel<View, true>), grid, block, 0, stream, view, A, d_bases, d_read_off, n_reads, d_order);
+        else
+            hipLaunchKernelGGL((anchors_kernel<View, false>), grid, block, 0, stream, view, A, d_bases, d_read_off, n_reads, d_order);
+    });
 }
 
 }  // namespace colbwt

@@ -179,6 +179,17 @@ int fail(int code, const std::string &msg) {
     return code;
 }
 
+const char *kNoSamples = "no locate samples attached (colbwt_index_attach_locate)";
+const char *kTooManyReads = "more than 2^32-2 reads in a batch";
+
+// kNoSamples unless every replica of the handle has its locate samples attached
+const char *samples_missing(const colbwt_index *idx) {
+    if (!idx->loc.ready()) return kNoSamples;
+    for (const colbwt_index *r : idx->more)
+        if (!r->loc.ready()) return kNoSamples;
+    return nullptr;
+}
+
 // A failed HIP call `what`: its colbwt code, with "<what>: <HIP's message>" in `msg`.  Whatever the
 // call queued on `stream` (nullptr: none of ours) is drained first: nothing of it may still be
 // running when the caller gets its arrays (and the next caller the staging buffers) back.
@@ -592,11 +603,8 @@ constexpr uint32_t kLocateMaxOcc = 1u << 20;
 int locate_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *read_off, uint64_t n_reads, uint32_t max_occ,
                      uint32_t *mlen, uint64_t *occ, uint64_t *pos, colbwt_stats *stats) {
     if (idx && (max_occ == 0 || max_occ > kLocateMaxOcc)) return fail(COLBWT_ERR_ARG, "max_occ must be 1 .. 2^20");
-    if (idx) {
-        if (!idx->loc.ready()) return fail(COLBWT_ERR_ARG, "no locate samples attached (colbwt_index_attach_locate)");
-        for (colbwt_index *r : idx->more)
-            if (!r->loc.ready()) return fail(COLBWT_ERR_ARG, "no locate samples attached (colbwt_index_attach_locate)");
-    }
+    if (idx)
+        if (const char *m = samples_missing(idx)) return fail(COLBWT_ERR_ARG, m);
     auto bad_pointers = [&](uint64_t n_bases) -> const char * {
         return (n_bases && !bases) || !mlen || !occ || !pos ? "null bases/mlen/occ/pos" : nullptr;
     };
@@ -639,11 +647,8 @@ const char *anchors_bad_params(uint32_t min_len, uint32_t max_anchors, uint32_t 
 const char *anchors_bad_setup(const colbwt_index *idx, uint32_t min_len, uint32_t max_anchors, uint32_t max_occ, const void *start,
                               const void *len, const void *occ, const void *pos) {
     if (const char *m = anchors_bad_params(min_len, max_anchors, max_occ)) return m;
-    if (max_occ > 0) {
-        if (!idx->loc.ready()) return "no locate samples attached (colbwt_index_attach_locate)";
-        for (const colbwt_index *r : idx->more)
-            if (!r->loc.ready()) return "no locate samples attached (colbwt_index_attach_locate)";
-    }
+    if (max_occ > 0)
+        if (const char *m = samples_missing(idx)) return m;
     if ((start != nullptr) != (len != nullptr) || (start != nullptr) != (occ != nullptr) ||
         (pos != nullptr) != (start != nullptr && max_occ > 0))
         return kAnchorsSlotSet;
@@ -675,7 +680,7 @@ int anchors_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *r
                       uint64_t *occ, uint64_t *pos, colbwt_stats *stats) {
     if (idx) {
         if (const char *m = anchors_bad_setup(idx, min_len, max_anchors, max_occ, start, len, occ, pos)) return fail(COLBWT_ERR_ARG, m);
-        if (n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, "more than 2^32-2 reads in a batch");
+        if (n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, kTooManyReads);
     }
     const uint64_t K = max_anchors, W = pos ? max_occ : 0;
     auto bad_pointers = [&](uint64_t n_bases) -> const char * {
@@ -733,9 +738,7 @@ const char *chain_bad_params(uint32_t max_anchors, uint32_t max_occ) {
 // The chain parameters, then the samples of every replica and their document count.
 const char *chain_bad_setup(const colbwt_index *idx, uint32_t max_anchors, uint32_t max_occ) {
     if (const char *m = chain_bad_params(max_anchors, max_occ)) return m;
-    if (!idx->loc.ready()) return "no locate samples attached (colbwt_index_attach_locate)";
-    for (const colbwt_index *r : idx->more)
-        if (!r->loc.ready()) return "no locate samples attached (colbwt_index_attach_locate)";
+    if (const char *m = samples_missing(idx)) return m;
     if (idx->loc.n_docs() > kDocsLds) return kDocsTooMany;
     return nullptr;
 }
@@ -788,7 +791,7 @@ int chain_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *rea
     if (idx) {
         if (min_len == 0) return fail(COLBWT_ERR_ARG, "min_len must be at least 1");
         if (const char *m = chain_bad_setup(idx, max_anchors, max_occ)) return fail(COLBWT_ERR_ARG, m);
-        if (n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, "more than 2^32-2 reads in a batch");
+        if (n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, kTooManyReads);
     }
     auto bad_pointers = [&](uint64_t n_bases) -> const char * { return (n_bases && !bases) || !chain ? "null bases/chain" : nullptr; };
     auto part = [&](colbwt_index *rep, uint64_t lo, uint64_t hi, uint64_t max_len, uint64_t min_read, colbwt_stats *st,
@@ -821,11 +824,9 @@ int docs_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *read
                    uint64_t *doc_only, colbwt_stats *stats) {
     if (idx) {
         if (const char *m = docs_bad_params(min_len, max_walk)) return fail(COLBWT_ERR_ARG, m);
-        if (!idx->loc.ready()) return fail(COLBWT_ERR_ARG, "no locate samples attached (colbwt_index_attach_locate)");
-        for (colbwt_index *r : idx->more)
-            if (!r->loc.ready()) return fail(COLBWT_ERR_ARG, "no locate samples attached (colbwt_index_attach_locate)");
+        if (const char *m = samples_missing(idx)) return fail(COLBWT_ERR_ARG, m);
         if (idx->loc.n_docs() > kDocsLds) return fail(COLBWT_ERR_ARG, kDocsTooMany);
-        if (n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, "more than 2^32-2 reads in a batch");
+        if (n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, kTooManyReads);
     }
     const uint32_t n_docs = idx ? idx->loc.n_docs() : 0, n_words = docs_mask_words(n_docs);
     const bool tally = doc_reads || doc_only;
@@ -878,9 +879,6 @@ int docs_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *read
     if (rc == COLBWT_OK && doc_only) std::copy(total.begin() + n_docs, total.end(), doc_only);
     return rc;
 }
-
-const char *kNoSamples = "no locate samples attached (colbwt_index_attach_locate)";
-const char *kTooManyReads = "more than 2^32-2 reads in a batch";
 
 // Where the shards of a colbwt_locate_all_batch call meet: a shard's positions start behind those of
 // the reads before it, and nothing may be written unless the whole batch fits, so every shard
@@ -944,9 +942,7 @@ int locate_all_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t
                          colbwt_stats *stats) {
     if (idx) {
         if (min_len == 0) return fail(COLBWT_ERR_ARG, "min_len must be at least 1");
-        if (!idx->loc.ready()) return fail(COLBWT_ERR_ARG, kNoSamples);
-        for (colbwt_index *r : idx->more)
-            if (!r->loc.ready()) return fail(COLBWT_ERR_ARG, kNoSamples);
+        if (const char *m = samples_missing(idx)) return fail(COLBWT_ERR_ARG, m);
         if (n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, kTooManyReads);
         if (n_reads == 0 && pos_off) pos_off[0] = 0;
     }
@@ -1042,7 +1038,7 @@ int seeds_batch_all(colbwt_index *idx, const uint8_t *bases, const uint64_t *rea
                     colbwt_stats *stats) {
     if (idx)
         if (const char *m = seeds_bad_params(min_len, max_seeds)) return fail(COLBWT_ERR_ARG, m);
-    if (idx && n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, "more than 2^32-2 reads in a batch");
+    if (idx && n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, kTooManyReads);
     const bool slots = seed_pos != nullptr;
     auto bad_pointers = [&](uint64_t n_bases) -> const char * {
         if ((n_bases && !bases) || !summary) return "null bases/summary";
@@ -1840,7 +1836,7 @@ int colbwt_seeds_reduce_device(const void *d_pml, int pml_bytes, const uint8_t *
     if (stats) memset(stats, 0, sizeof(*stats));
     if (pml_bytes != 2 && pml_bytes != 4) return fail(COLBWT_ERR_ARG, "pml_bytes must be 2 or 4");
     if (const char *m = seeds_bad_params(min_len, max_seeds)) return fail(COLBWT_ERR_ARG, m);
-    if (n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, "more than 2^32-2 reads in a batch");
+    if (n_reads >= 0xFFFFFFFFull) return fail(COLBWT_ERR_ARG, kTooManyReads);
     if ((d_seed_pos != nullptr) != (d_seed_len != nullptr) || (d_seed_pos != nullptr) != (d_seed_cid != nullptr))
         return fail(COLBWT_ERR_ARG, "d_seed_pos/d_seed_len/d_seed_cid: all three or none");
     if (n_reads == 0) return COLBWT_OK;
@@ -1931,7 +1927,7 @@ int colbwt_index_attach_locate(colbwt_index *idx, const char *prefix_or_file) {
 
 int colbwt_locate_docs(const colbwt_index *idx, uint64_t *doc_start, uint32_t cap, uint32_t *n_docs) {
     if (!idx || !n_docs) return fail(COLBWT_ERR_ARG, "null argument");
-    if (!idx->loc.ready()) return fail(COLBWT_ERR_ARG, "no locate samples attached (colbwt_index_attach_locate)");
+    if (!idx->loc.ready()) return fail(COLBWT_ERR_ARG, kNoSamples);
     const std::vector<uint64_t> &ds = idx->loc.doc_start;
     *n_docs = (uint32_t)ds.size();
     if (!doc_start || cap < ds.size()) return fail(COLBWT_ERR_ARG, "doc_start holds fewer than n_docs entries");
@@ -1949,9 +1945,7 @@ int colbwt_locate_device(colbwt_index *idx, const uint8_t *d_bases, const uint64
                          const uint32_t *d_order, void *hip_stream, colbwt_stats *stats) {
     auto bad_argument = [&]() -> const char * {
         if (max_occ == 0 || max_occ > kLocateMaxOcc) return "max_occ must be 1 .. 2^20";
-        if (!idx->loc.ready()) return "no locate samples attached (colbwt_index_attach_locate)";
-        for (colbwt_index *r : idx->more)
-            if (!r->loc.ready()) return "no locate samples attached (colbwt_index_attach_locate)";
+        if (const char *m = samples_missing(idx)) return m;
         if (n_reads == 0) return nullptr;
         if (!d_bases || !d_read_off || !d_mlen || !d_occ || !d_pos) return "null device pointer";
         if (((uintptr_t)d_bases & 15) || ((uintptr_t)d_mlen & 3) || ((uintptr_t)d_occ & 7) || ((uintptr_t)d_pos & 7))
@@ -1970,7 +1964,7 @@ int colbwt_locate_file(colbwt_index *idx, const char *pattern_path, const char *
                        uint64_t batch_bases, colbwt_stats *stats) {
     if (!idx || !pattern_path) return fail(COLBWT_ERR_ARG, "null argument");
     if (max_occ == 0 || max_occ > kLocateMaxOcc) return fail(COLBWT_ERR_ARG, "max_occ must be 1 .. 2^20");
-    if (!idx->loc.ready()) return fail(COLBWT_ERR_ARG, "no locate samples attached (colbwt_index_attach_locate)");
+    if (!idx->loc.ready()) return fail(COLBWT_ERR_ARG, kNoSamples);
     const std::string out = out_path ? out_path : std::string(pattern_path) + ".locate";
     if (batch_bases == 0)   // the default batch of the file query, cut so that max_occ slots per read stay ~tens of MB
         batch_bases = std::max<uint64_t>(1ull << 20, (64ull << 20) * (1 + idx->more.size()) * 16 / std::max<uint32_t>(16, max_occ));
@@ -1990,7 +1984,7 @@ int colbwt_anchors_device(colbwt_index *idx, const uint8_t *d_bases, const uint6
                           void *hip_stream, colbwt_stats *stats) {
     auto bad_argument = [&]() -> const char * {
         if (const char *m = anchors_bad_setup(idx, min_len, max_anchors, max_occ, d_start, d_len, d_occ, d_pos)) return m;
-        if (n_reads >= 0xFFFFFFFFull) return "more than 2^32-2 reads in a batch";
+        if (n_reads >= 0xFFFFFFFFull) return kTooManyReads;
         if (n_reads == 0) return nullptr;
         if (!d_bases || !d_read_off || !d_summary) return "null device pointer";
         if (((uintptr_t)d_bases & 15) || ((uintptr_t)d_summary & 15) || ((uintptr_t)d_start & 3) || ((uintptr_t)d_len & 3) ||
@@ -2011,7 +2005,7 @@ int colbwt_anchors_file(colbwt_index *idx, const char *pattern_path, const char 
                         uint32_t max_occ, uint64_t batch_bases, colbwt_stats *stats) {
     if (!idx || !pattern_path) return fail(COLBWT_ERR_ARG, "null argument");
     if (const char *m = anchors_bad_params(min_len, max_anchors, max_occ)) return fail(COLBWT_ERR_ARG, m);
-    if (max_occ > 0 && !idx->loc.ready()) return fail(COLBWT_ERR_ARG, "no locate samples attached (colbwt_index_attach_locate)");
+    if (max_occ > 0 && !idx->loc.ready()) return fail(COLBWT_ERR_ARG, kNoSamples);
     const std::string out = out_path ? out_path : std::string(pattern_path) + ".anchors";
     if (batch_bases == 0) {   // the default batch of the file query, cut by the slot bytes per read as locate cuts it by max_occ
         const uint64_t slot_bytes = (uint64_t)max_anchors * (16 + 8 * (uint64_t)max_occ);
@@ -2029,7 +2023,7 @@ int colbwt_chain_reduce_device(colbwt_index *idx, const uint32_t *d_start, const
                                void *hip_stream, colbwt_stats *stats) {
     auto bad_argument = [&]() -> const char * {
         if (const char *m = chain_bad_setup(idx, max_anchors, max_occ)) return m;
-        if (n_reads >= 0xFFFFFFFFull) return "more than 2^32-2 reads in a batch";
+        if (n_reads >= 0xFFFFFFFFull) return kTooManyReads;
         if (n_reads == 0) return nullptr;
         if (!d_start || !d_len || !d_pos || !d_chain) return "null device pointer";
         if (((uintptr_t)d_start & 3) || ((uintptr_t)d_len & 3) || ((uintptr_t)d_pos & 7) || ((uintptr_t)d_chain & 15))
@@ -2051,7 +2045,7 @@ int colbwt_chain_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_
     auto bad_argument = [&]() -> const char * {
         if (min_len == 0) return "min_len must be at least 1";
         if (const char *m = chain_bad_setup(idx, max_anchors, max_occ)) return m;
-        if (n_reads >= 0xFFFFFFFFull) return "more than 2^32-2 reads in a batch";
+        if (n_reads >= 0xFFFFFFFFull) return kTooManyReads;
         if (n_reads == 0) return nullptr;
         if (!d_bases || !d_read_off || !d_chain || !d_work) return "null device pointer";
         if (((uintptr_t)d_bases & 15) || ((uintptr_t)d_chain & 15)) return "d_bases/d_chain must be 16-byte aligned";
@@ -2096,9 +2090,7 @@ int colbwt_locate_all_plan_device(colbwt_index *idx, const uint8_t *d_bases, con
                                   colbwt_stats *stats) {
     auto bad_argument = [&]() -> const char * {
         if (min_len == 0) return "min_len must be at least 1";
-        if (!idx->loc.ready()) return kNoSamples;
-        for (colbwt_index *r : idx->more)
-            if (!r->loc.ready()) return kNoSamples;
+        if (const char *m = samples_missing(idx)) return m;
         if (n_reads == 0) return nullptr;
         if (!d_bases || !d_read_off || !d_mlen || !d_occ) return "null device pointer";
         if (((uintptr_t)d_bases & 15) || ((uintptr_t)d_mlen & 3) || ((uintptr_t)d_occ & 7))
@@ -2137,9 +2129,7 @@ int colbwt_locate_all_plan_device(colbwt_index *idx, const uint8_t *d_bases, con
 int colbwt_locate_all_fill_device(colbwt_index *idx, uint64_t n_reads, uint64_t read_lo, uint64_t read_hi, const uint64_t *d_pos_off,
                                   uint64_t *d_pos, uint64_t pos_cap, const void *d_work, void *hip_stream, colbwt_stats *stats) {
     auto bad_argument = [&]() -> const char * {
-        if (!idx->loc.ready()) return kNoSamples;
-        for (colbwt_index *r : idx->more)
-            if (!r->loc.ready()) return kNoSamples;
+        if (const char *m = samples_missing(idx)) return m;
         if (read_lo > read_hi || read_hi > n_reads) return "read_lo <= read_hi <= n_reads expected";
         if (n_reads >= 0xFFFFFFFFull) return kTooManyReads;
         if (read_lo == read_hi) return nullptr;
@@ -2299,15 +2289,13 @@ int colbwt_docs_device(colbwt_index *idx, const uint8_t *d_bases, const uint64_t
                        colbwt_stats *stats) {
     auto bad_argument = [&]() -> const char * {
         if (const char *m = docs_bad_params(min_len, max_walk)) return m;
-        if (!idx->loc.ready()) return "no locate samples attached (colbwt_index_attach_locate)";
-        for (colbwt_index *r : idx->more)
-            if (!r->loc.ready()) return "no locate samples attached (colbwt_index_attach_locate)";
+        if (const char *m = samples_missing(idx)) return m;
         if (idx->loc.n_docs() > kDocsLds) return kDocsTooMany;
         if (n_reads == 0) return nullptr;
         if (!d_bases || !d_read_off || !d_mlen || !d_occ) return "null device pointer";
         if (((uintptr_t)d_bases & 15) || ((uintptr_t)d_mlen & 3) || ((uintptr_t)d_occ & 7))
             return "d_bases must be 16-byte aligned, d_mlen 4-byte and d_occ 8-byte aligned";
-        if (n_reads >= 0xFFFFFFFFull) return "more than 2^32-2 reads in a batch";
+        if (n_reads >= 0xFFFFFFFFull) return kTooManyReads;
         if (!d_n_hit || !d_mask || !d_work) return "null d_n_hit/d_mask/d_work";
         if (((uintptr_t)d_n_hit & 3) || ((uintptr_t)d_mask & 7) || ((uintptr_t)d_doc_reads & 7) || ((uintptr_t)d_doc_only & 7))
             return "d_n_hit must be 4-byte aligned, d_mask/d_doc_reads/d_doc_only 8-byte aligned";
@@ -2329,7 +2317,7 @@ int colbwt_docs_file(colbwt_index *idx, const char *pattern_path, const char *ou
                      uint64_t batch_bases, colbwt_stats *stats) {
     if (!idx || !pattern_path) return fail(COLBWT_ERR_ARG, "null argument");
     if (const char *m = docs_bad_params(min_len, max_walk)) return fail(COLBWT_ERR_ARG, m);
-    if (!idx->loc.ready()) return fail(COLBWT_ERR_ARG, "no locate samples attached (colbwt_index_attach_locate)");
+    if (!idx->loc.ready()) return fail(COLBWT_ERR_ARG, kNoSamples);
     if (idx->loc.n_docs() > kDocsLds) return fail(COLBWT_ERR_ARG, kDocsTooMany);
     const std::string out = out_path ? out_path : std::string(pattern_path) + ".docs";
     if (batch_bases == 0)   // the default batch of the file query, cut so that W mask words per read stay ~tens of MB

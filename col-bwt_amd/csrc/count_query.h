@@ -142,12 +142,96 @@ __device__ __forceinline__ void count_fast_forward(const V &view, uint32_t &j, u
     w = view.load(j);
 }
 
+// The (row, offset) cursors of [sp, ep] with the rows they lie in, and toe = SA[ep] (kToe only).
 template <class V>
-__global__ __launch_bounds__(kQueryBlock) void count_kernel(V view, const uint8_t *__restrict__ bases,
-                                                            const uint64_t *__restrict__ read_off, uint64_t n_reads,
-                                                            uint32_t *__restrict__ mlen_out, uint64_t *__restrict__ occ_out,
-                                                            uint64_t *__restrict__ sp_out, const uint32_t *__restrict__ order) {
+struct SearchRange {
     using Row = typename V::Row;
+    uint32_t js, je;
+    uint64_t os, oe;
+    Row ws, we;
+    uint32_t toe;
+    // [0, n - 1]: row 0 offset 0 .. the last row at its last offset
+    template <bool kToe>
+    __device__ __forceinline__ void full(const V &view, const uint32_t *__restrict__ toe_row) {
+        js = 0;
+        je = view.rows() - 1;
+        ws = view.load(js);
+        we = view.load(je);
+        os = 0;
+        oe = view.len(je, we) - 1;
+        toe = 0;
+        if constexpr (kToe) toe = toe_row[je];   // SA[n - 1]
+    }
+};
+
+// One backward-search step with character c (cidx = its column of the jump tables): the only copy of
+// the step, called by count, locate, locate-all and anchors.  kToe: whether the toehold SA[ep]
+// (locate_query.h) is carried; without it toe_row is never loaded and may be null.
+// True: R is the range of c + (what R matched).  False: no such range (c does not occur in R, or LF
+// left an empty range); R is unchanged.
+template <bool kToe, class V>
+__device__ __forceinline__ bool search_step(const V &view, const uint32_t *__restrict__ toe_row, uint32_t c, uint32_t cidx,
+                                            SearchRange<V> &R) {
+    using Row = typename V::Row;
+    // s: first position >= sp holding c
+    uint32_t sj = R.js;
+    uint64_t so = R.os;
+    Row sw = R.ws;
+    if (view.ch(R.ws) != c) {
+        sj = view.succ(R.js, c, cidx, sw);
+        if (sj == kNone) return false;
+        so = 0;
+    }
+    // e: last position <= ep holding c
+    uint32_t ej = R.je;
+    uint64_t eo = R.oe;
+    Row ew = R.we;
+    uint32_t te = R.toe;                 // SA[e]
+    if (view.ch(R.we) != c) {
+        ej = view.pred(R.je, c, cidx, ew);
+        if (ej == kNone) return false;
+        eo = view.len(ej, ew) - 1;
+        if constexpr (kToe) te = toe_row[ej];
+    }
+    if (sj > ej || (sj == ej && so > eo)) return false;
+    // LF of both ends
+    uint32_t nj = view.lf_row(sw);
+    uint64_t nt = (uint64_t)view.lf_off(sw) + so;
+    Row nw = view.load(nj);
+    count_fast_forward(view, nj, nt, nw);
+    uint32_t mj;
+    uint64_t mt;
+    Row mw;
+    if (sj == ej) {                      // one row: the image of [so, eo] is contiguous
+        mj = nj;
+        mt = nt + (eo - so);
+        mw = nw;
+    } else {
+        mj = view.lf_row(ew);
+        mt = (uint64_t)view.lf_off(ew) + eo;
+        mw = view.load(mj);
+    }
+    count_fast_forward(view, mj, mt, mw);
+    if (nj > mj || (nj == mj && nt > mt)) return false;   // empty range: only on synthetic tables
+    R.js = nj; R.os = nt; R.ws = nw;
+    R.je = mj; R.oe = mt; R.we = mw;
+    R.toe = te - 1;
+    return true;
+}
+
+// The longest suffix of the lane's read that occurs in the text: the frame count, locate and
+// locate-all share.  The jump-table columns go to LDS, the lane takes read order[lane] (or its own),
+// and the read's bases go through search_step from the last one down until one has no range.
+// kStopLow: a byte <= 1 ends the search as an absent character does (count walks through them).
+// A lane with a read ends in done(rd, k, R): rd = its read, k = the bases consumed, R = the last
+// non-empty range (the full one when k == 0); a lane past n_reads returns without it.  The kernel's
+// own epilogue is that callable and not code behind a returned k: so the lane's values and its early
+// return stay in one function, and the kernels keep the registers they had with the loop written out.
+// The window refill is at the top of a trip, where the wave is converged (lane_io.h).
+template <bool kToe, bool kStopLow, class V, class Done>
+__device__ __forceinline__ void longest_suffix(const V &view, const uint32_t *__restrict__ toe_row,
+                                               const uint8_t *__restrict__ bases, const uint64_t *__restrict__ read_off,
+                                               uint64_t n_reads, const uint32_t *__restrict__ order, Done &&done) {
     __shared__ uint32_t s_rd[16][kQueryBlock];
     __shared__ uint8_t s_cmap[256];
     for (uint32_t t = threadIdx.x; t < 256; t += kQueryBlock) s_cmap[t] = view.cmap()[t];
@@ -159,12 +243,9 @@ __global__ __launch_bounds__(kQueryBlock) void count_kernel(V view, const uint8_
     const uint64_t off = read_off[rd];
     const uint64_t m = read_off[rd + 1] - off;
 
-    // [sp, ep] = [0, n - 1]: row 0 offset 0 .. row r-1 at its last offset
-    uint32_t js = 0, je = view.rows() - 1;
-    Row ws = view.load(js), we = view.load(je);
-    uint64_t os = 0, oe = view.len(je, we) - 1;
-    uint64_t k = 0;   // bases consumed
-
+    SearchRange<V> R;
+    R.template full<kToe>(view, toe_row);
+    uint64_t k = 0;
     SlidingWindow win;
     win.init(off + m - 1);
     for (; k < m; ++k) {
@@ -172,78 +253,51 @@ __global__ __launch_bounds__(kQueryBlock) void count_kernel(V view, const uint8_
         if (__any(win.avail(g) < 1)) win.refill(s_rd, bases, g);
         const uint32_t c = win.get(s_rd, g);
         const uint32_t cidx = s_cmap[c];
-        if (cidx == kAbsent) break;
-        // s: first position >= sp holding c
-        uint32_t sj = js;
-        uint64_t so = os;
-        Row sw = ws;
-        if (view.ch(ws) != c) {
-            sj = view.succ(js, c, cidx, sw);
-            if (sj == kNone) break;
-            so = 0;
-        }
-        // e: last position <= ep holding c
-        uint32_t ej = je;
-        uint64_t eo = oe;
-        Row ew = we;
-        if (view.ch(we) != c) {
-            ej = view.pred(je, c, cidx, ew);
-            if (ej == kNone) break;
-            eo = view.len(ej, ew) - 1;
-        }
-        if (sj > ej || (sj == ej && so > eo)) break;
-        // LF of both ends
-        uint32_t nj = view.lf_row(sw);
-        uint64_t nt = (uint64_t)view.lf_off(sw) + so;
-        Row nw = view.load(nj);
-        count_fast_forward(view, nj, nt, nw);
-        uint32_t mj;
-        uint64_t mt;
-        Row mw;
-        if (sj == ej) {                  // one row: the image of [so, eo] is contiguous
-            mj = nj;
-            mt = nt + (eo - so);
-            mw = nw;
-        } else {
-            mj = view.lf_row(ew);
-            mt = (uint64_t)view.lf_off(ew) + eo;
-            mw = view.load(mj);
-        }
-        count_fast_forward(view, mj, mt, mw);
-        if (nj > mj || (nj == mj && nt > mt)) break;   // empty range: only on synthetic tables
-        js = nj; os = nt; ws = nw;
-        je = mj; oe = mt; we = mw;
+        if ((kStopLow && c <= 1) || cidx == kAbsent) break;
+        if (!search_step<kToe>(view, toe_row, c, cidx, R)) break;
     }
-    uint64_t occ = 0, sp = 0;
-    if (k > 0) {
-        sp = view.idx(js) + os;
-        occ = view.idx(je) + oe - sp + 1;
-    }
-    mlen_out[rd] = (uint32_t)k;
-    occ_out[rd] = occ;
-    if (sp_out) sp_out[rd] = sp;
+    done(rd, k, R);
 }
 
-template <typename View>
-inline void launch_count_view(const View &view, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads,
-                              uint32_t *d_mlen, uint64_t *d_occ, uint64_t *d_sp, const uint32_t *d_order, hipStream_t stream) {
-    const dim3 grid((uint32_t)((n_reads + kQueryBlock - 1) / kQueryBlock)), block(kQueryBlock);
-    hipLaunchKernelGGL(count_kernel<View>, grid, block, 0, stream, view, d_bases, d_read_off, n_reads, d_mlen, d_occ, d_sp,
-                       d_order);
+template <class V>
+__global__ __launch_bounds__(kQueryBlock) void count_kernel(V view, const uint8_t *__restrict__ bases,
+                                                            const uint64_t *__restrict__ read_off, uint64_t n_reads,
+                                                            uint32_t *__restrict__ mlen_out, uint64_t *__restrict__ occ_out,
+                                                            uint64_t *__restrict__ sp_out, const uint32_t *__restrict__ order) {
+    longest_suffix<false, false>(view, nullptr, bases, read_off, n_reads, order,
+                                 [&](uint64_t rd, uint64_t k, const SearchRange<V> &R) {
+                                     uint64_t occ = 0, sp = 0;
+                                     if (k > 0) {
+                                         sp = view.idx(R.js) + R.os;
+                                         occ = view.idx(R.je) + R.oe - sp + 1;
+                                     }
+                                     mlen_out[rd] = (uint32_t)k;
+                                     occ_out[rd] = occ;
+                                     if (sp_out) sp_out[rd] = sp;
+                                 });
 }
 
-// Count queries over whatever layout the index holds (exactly one of its tables is live).
+// Calls f(view) with the View of the layout the index holds (exactly one of its tables is live):
+// the only place that maps a layout to its View.
+template <class F>
+inline auto with_view(const Index &ix, F &&f) {
+    if (ix.line_rows()) return f(CountFatView{ix.table_fat()});
+    if (ix.layout() == 3) return f(CountSKView<3>{ix.table_k()});
+    if (ix.layout() == 2) return f(CountSKView<2>{ix.table_k()});
+    return f(CountOneStepView{ix.table()});
+}
+
+// one lane per read
+inline dim3 read_grid(uint64_t n_reads) { return dim3((uint32_t)((n_reads + kQueryBlock - 1) / kQueryBlock)); }
+
+// Count queries over whatever layout the index holds.
 inline void launch_count(const Index &ix, const uint8_t *d_bases, const uint64_t *d_read_off, uint64_t n_reads,
                          uint32_t *d_mlen, uint64_t *d_occ, uint64_t *d_sp, const uint32_t *d_order, hipStream_t stream) {
     if (n_reads == 0) return;
-    if (ix.line_rows())
-        launch_count_view(CountFatView{ix.table_fat()}, d_bases, d_read_off, n_reads, d_mlen, d_occ, d_sp, d_order, stream);
-    else if (ix.layout() == 3)
-        launch_count_view(CountSKView<3>{ix.table_k()}, d_bases, d_read_off, n_reads, d_mlen, d_occ, d_sp, d_order, stream);
-    else if (ix.layout() == 2)
-        launch_count_view(CountSKView<2>{ix.table_k()}, d_bases, d_read_off, n_reads, d_mlen, d_occ, d_sp, d_order, stream);
-    else
-        launch_count_view(CountOneStepView{ix.table()}, d_bases, d_read_off, n_reads, d_mlen, d_occ, d_sp, d_order, stream);
+    with_view(ix, [&](auto view) {
+        hipLaunchKernelGGL(count_kernel<decltype(view)>, read_grid(n_reads), dim3(kQueryBlock), 0, stream, view, d_bases, d_read_off,
+                           n_reads, d_mlen, d_occ, d_sp, d_order);
+    });
 }
 
 }  // namespace colbwt

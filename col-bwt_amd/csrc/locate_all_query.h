@@ -2,10 +2,8 @@
 // rows (include/colbwt.h, colbwt_locate_all_*), gfx950, wave64.  Included by capi.hip only.
 //
 // Three stages over a caller-provided workspace (LocAllWork), none of them with an atomic:
-//   search  locate_all_search_kernel: locate_kernel's backward search (locate_query.h) without its
-//           walk.  Per read it leaves mlen, occ, toe = SA[ep] and the BWT position of ep.  The ~70
-//           lines of the search loop are a deliberate copy: locate_kernel's source stays as it is
-//           (DESIGN.md section 12).
+//   search  locate_all_search_kernel: locate_kernel's backward search (the same longest_suffix call)
+//           without its walk.  Per read it leaves mlen, occ, toe = SA[ep] and the BWT position of ep.
 //   plan    locate_all_width_kernel stores w (the positions the read gets) into pos_off[k + 1] and
 //           ceil(w / C) into tile_off[k + 1], C = kLocAllTile; two in-place inclusive scans turn both
 //           into offsets.  Entry 0 of either array is stored by the kernel.
@@ -72,7 +70,7 @@ inline LocAllWork locate_all_work(const void *d_work, uint64_t n_reads) {
     return w;
 }
 
-// locate_kernel's search (locate_query.h), kept in step with it by hand; what differs is the end.
+// locate_kernel's search (count_query.h longest_suffix); what differs is what it stores afterwards.
 template <class V>
 __global__ __launch_bounds__(kQueryBlock) void locate_all_search_kernel(V view, const uint32_t *__restrict__ toe_row,
                                                                         const uint8_t *__restrict__ bases,
@@ -80,80 +78,16 @@ __global__ __launch_bounds__(kQueryBlock) void locate_all_search_kernel(V view, 
                                                                         uint32_t *__restrict__ mlen_out, uint64_t *__restrict__ occ_out,
                                                                         uint32_t *__restrict__ toe_out, uint64_t *__restrict__ ep_out,
                                                                         const uint32_t *__restrict__ order) {
-    using Row = typename V::Row;
-    __shared__ uint32_t s_rd[16][kQueryBlock];
-    __shared__ uint8_t s_cmap[256];
-    for (uint32_t t = threadIdx.x; t < 256; t += kQueryBlock) s_cmap[t] = view.cmap()[t];
-    __syncthreads();
-
-    const uint64_t slot = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
-    if (slot >= n_reads) return;
-    const uint64_t rd = order ? order[slot] : slot;
-    const uint64_t off = read_off[rd];
-    const uint64_t m = read_off[rd + 1] - off;
-
-    uint32_t js = 0, je = view.rows() - 1;
-    Row ws = view.load(js), we = view.load(je);
-    uint64_t os = 0, oe = view.len(je, we) - 1;
-    uint32_t toe = toe_row[je];   // SA[n - 1]
-    uint64_t k = 0;
-
-    SlidingWindow win;
-    win.init(off + m - 1);
-    for (; k < m; ++k) {
-        const uint64_t g = off + m - 1 - k;
-        if (__any(win.avail(g) < 1)) win.refill(s_rd, bases, g);
-        const uint32_t c = win.get(s_rd, g);
-        const uint32_t cidx = s_cmap[c];
-        if (c <= 1 || cidx == kAbsent) break;
-        uint32_t sj = js;
-        uint64_t so = os;
-        Row sw = ws;
-        if (view.ch(ws) != c) {
-            sj = view.succ(js, c, cidx, sw);
-            if (sj == kNone) break;
-            so = 0;
-        }
-        uint32_t ej = je;
-        uint64_t eo = oe;
-        Row ew = we;
-        uint32_t te = toe;                 // SA[e]
-        if (view.ch(we) != c) {
-            ej = view.pred(je, c, cidx, ew);
-            if (ej == kNone) break;
-            eo = view.len(ej, ew) - 1;
-            te = toe_row[ej];
-        }
-        if (sj > ej || (sj == ej && so > eo)) break;
-        uint32_t nj = view.lf_row(sw);
-        uint64_t nt = (uint64_t)view.lf_off(sw) + so;
-        Row nw = view.load(nj);
-        count_fast_forward(view, nj, nt, nw);
-        uint32_t mj;
-        uint64_t mt;
-        Row mw;
-        if (sj == ej) {
-            mj = nj;
-            mt = nt + (eo - so);
-            mw = nw;
-        } else {
-            mj = view.lf_row(ew);
-            mt = (uint64_t)view.lf_off(ew) + eo;
-            mw = view.load(mj);
-        }
-        count_fast_forward(view, mj, mt, mw);
-        if (nj > mj || (nj == mj && nt > mt)) break;
-        js = nj; os = nt; ws = nw;
-        je = mj; oe = mt; we = mw;
-        toe = te - 1;
-    }
-    const uint64_t ep = view.idx(je) + oe;
-    uint64_t occ = 0;
-    if (k > 0) occ = ep - (view.idx(js) + os) + 1;
-    mlen_out[rd] = (uint32_t)k;
-    occ_out[rd] = occ;
-    toe_out[rd] = toe;
-    ep_out[rd] = ep;
+    longest_suffix<true, true>(view, toe_row, bases, read_off, n_reads, order,
+                               [&](uint64_t rd, uint64_t k, const SearchRange<V> &R) {
+                                   const uint64_t ep = view.idx(R.je) + R.oe;
+                                   uint64_t occ = 0;
+                                   if (k > 0) occ = ep - (view.idx(R.js) + R.os) + 1;
+                                   mlen_out[rd] = (uint32_t)k;
+                                   occ_out[rd] = occ;
+                                   toe_out[rd] = R.toe;
+                                   ep_out[rd] = ep;
+                               });
 }
 
 // w = the positions read k gets, its tiles = ceil(w / C): the inputs of the two scans, in place
@@ -255,15 +189,6 @@ struct LocAllArgs {
     PhiTable phi;
 };
 
-template <typename View>
-inline void launch_locate_all_search_view(const View &view, const uint32_t *toe_row, const uint8_t *d_bases, const uint64_t *d_read_off,
-                                          uint64_t n_reads, uint32_t *d_mlen, uint64_t *d_occ, uint32_t *d_toe, uint64_t *d_ep,
-                                          const uint32_t *d_order, hipStream_t stream) {
-    const dim3 grid((uint32_t)((n_reads + kQueryBlock - 1) / kQueryBlock)), block(kQueryBlock);
-    hipLaunchKernelGGL(locate_all_search_kernel<View>, grid, block, 0, stream, view, toe_row, d_bases, d_read_off, n_reads, d_mlen,
-                       d_occ, d_toe, d_ep, d_order);
-}
-
 // Search and plan for a batch in HBM: d_mlen / d_occ n_reads entries, d_pos_off n_reads + 1.  d_order
 // goes to the search only.
 inline hipError_t launch_locate_all_plan(const Index &ix, const LocAllArgs &a, const uint8_t *d_bases, const uint64_t *d_read_off,
@@ -271,18 +196,10 @@ inline hipError_t launch_locate_all_plan(const Index &ix, const LocAllArgs &a, c
                                          uint64_t *d_pos_off, void *d_work, const uint32_t *d_order, hipStream_t stream) {
     if (n_reads == 0) return hipSuccess;
     const LocAllWork w = locate_all_work(d_work, n_reads);
-    if (ix.line_rows())
-        launch_locate_all_search_view(CountFatView{ix.table_fat()}, a.toe_row, d_bases, d_read_off, n_reads, d_mlen, d_occ, w.toe, w.ep,
-                                      d_order, stream);
-    else if (ix.layout() == 3)
-        launch_locate_all_search_view(CountSKView<3>{ix.table_k()}, a.toe_row, d_bases, d_read_off, n_reads, d_mlen, d_occ, w.toe, w.ep,
-                                      d_order, stream);
-    else if (ix.layout() == 2)
-        launch_locate_all_search_view(CountSKView<2>{ix.table_k()}, a.toe_row, d_bases, d_read_off, n_reads, d_mlen, d_occ, w.toe, w.ep,
-                                      d_order, stream);
-    else
-        launch_locate_all_search_view(CountOneStepView{ix.table()}, a.toe_row, d_bases, d_read_off, n_reads, d_mlen, d_occ, w.toe, w.ep,
-                                      d_order, stream);
+    with_view(ix, [&](auto view) {
+        hipLaunchKernelGGL(locate_all_search_kernel<decltype(view)>, read_grid(n_reads), dim3(kQueryBlock), 0, stream, view, a.toe_row,
+                           d_bases, d_read_off, n_reads, d_mlen, d_occ, w.toe, w.ep, d_order);
+    });
 
     const dim3 grid((uint32_t)((n_reads + kLocAllBlock - 1) / kLocAllBlock)), block(kLocAllBlock);
     hipLaunchKernelGGL(locate_all_width_kernel, grid, block, 0, stream, d_mlen, d_occ, n_reads, min_len, max_per_read, d_pos_off,
@@ -312,26 +229,15 @@ inline uint32_t locate_all_fill_grid() {
     return blocks[dev];
 }
 
-template <typename View>
-inline void launch_locate_all_walk_view(const View &view, const LocAllArgs &a, const uint64_t *d_pos_off, const LocAllWork &w,
-                                        uint64_t read_lo, uint64_t read_hi, uint64_t *d_pos, uint64_t pos_cap, hipStream_t stream) {
-    hipLaunchKernelGGL(locate_all_walk_kernel<View>, dim3(locate_all_fill_grid()), dim3(kLocAllBlock), 0, stream, view, a.toe_row, a.phi,
-                       d_pos_off, w.tile_off, w.ep, w.toe, read_lo, read_hi, d_pos, pos_cap);
-}
-
 // The walk over the reads [read_lo, read_hi) of a planned batch into d_pos[0 .. pos_cap).
 inline void launch_locate_all_fill(const Index &ix, const LocAllArgs &a, uint64_t n_reads, uint64_t read_lo, uint64_t read_hi,
                                    const uint64_t *d_pos_off, uint64_t *d_pos, uint64_t pos_cap, const void *d_work, hipStream_t stream) {
     if (read_lo >= read_hi) return;
     const LocAllWork w = locate_all_work(d_work, n_reads);
-    if (ix.line_rows())
-        launch_locate_all_walk_view(CountFatView{ix.table_fat()}, a, d_pos_off, w, read_lo, read_hi, d_pos, pos_cap, stream);
-    else if (ix.layout() == 3)
-        launch_locate_all_walk_view(CountSKView<3>{ix.table_k()}, a, d_pos_off, w, read_lo, read_hi, d_pos, pos_cap, stream);
-    else if (ix.layout() == 2)
-        launch_locate_all_walk_view(CountSKView<2>{ix.table_k()}, a, d_pos_off, w, read_lo, read_hi, d_pos, pos_cap, stream);
-    else
-        launch_locate_all_walk_view(CountOneStepView{ix.table()}, a, d_pos_off, w, read_lo, read_hi, d_pos, pos_cap, stream);
+    with_view(ix, [&](auto view) {
+        hipLaunchKernelGGL(locate_all_walk_kernel<decltype(view)>, dim3(locate_all_fill_grid()), dim3(kLocAllBlock), 0, stream, view,
+                           a.toe_row, a.phi, d_pos_off, w.tile_off, w.ep, w.toe, read_lo, read_hi, d_pos, pos_cap);
+    });
 }
 
 }  // namespace colbwt

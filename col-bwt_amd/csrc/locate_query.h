@@ -1,9 +1,9 @@
 // locate_query.h -- text positions of each read's longest exact match (r-index toehold + phi) over
 // every HBM layout of the index, gfx950, wave64.  Included by capi.hip only.
 //
-// The search is count_query.h's backward search, with the read's bytes <= 1 ending it (the folded
-// separator / terminator class: the table's LF is not the text's LF there).  Besides the (row, offset)
-// cursors of [sp, ep] the lane carries toe = SA[ep]:
+// The search is count_query.h's longest_suffix / search_step with kToe, and with the read's bytes <= 1
+// ending it (the folded separator / terminator class: the table's LF is not the text's LF there).
+// Besides the (row, offset) cursors of [sp, ep] the range then carries toe = SA[ep]:
 //   ep stays in its row (the row holds c)    SA[LF(ep)] = SA[ep] - 1            toe -= 1
 //   ep moves to pred(c), the last position   that position ends a folded run:  toe = toe_row[row] - 1
 //   of a row that ends a run
@@ -54,85 +54,21 @@ __global__ __launch_bounds__(kQueryBlock) void locate_kernel(V view, const uint3
                                                              uint32_t max_occ, uint32_t *__restrict__ mlen_out,
                                                              uint64_t *__restrict__ occ_out, uint64_t *__restrict__ pos_out,
                                                              const uint32_t *__restrict__ order) {
-    using Row = typename V::Row;
-    __shared__ uint32_t s_rd[16][kQueryBlock];
-    __shared__ uint8_t s_cmap[256];
-    for (uint32_t t = threadIdx.x; t < 256; t += kQueryBlock) s_cmap[t] = view.cmap()[t];
-    __syncthreads();
-
-    const uint64_t slot = (uint64_t)blockIdx.x * kQueryBlock + threadIdx.x;
-    if (slot >= n_reads) return;
-    const uint64_t rd = order ? order[slot] : slot;
-    const uint64_t off = read_off[rd];
-    const uint64_t m = read_off[rd + 1] - off;
-
-    uint32_t js = 0, je = view.rows() - 1;
-    Row ws = view.load(js), we = view.load(je);
-    uint64_t os = 0, oe = view.len(je, we) - 1;
-    uint32_t toe = toe_row[je];   // SA[n - 1]
-    uint64_t k = 0;
-
-    SlidingWindow win;
-    win.init(off + m - 1);
-    for (; k < m; ++k) {
-        const uint64_t g = off + m - 1 - k;
-        if (__any(win.avail(g) < 1)) win.refill(s_rd, bases, g);
-        const uint32_t c = win.get(s_rd, g);
-        const uint32_t cidx = s_cmap[c];
-        if (c <= 1 || cidx == kAbsent) break;
-        uint32_t sj = js;
-        uint64_t so = os;
-        Row sw = ws;
-        if (view.ch(ws) != c) {
-            sj = view.succ(js, c, cidx, sw);
-            if (sj == kNone) break;
-            so = 0;
-        }
-        uint32_t ej = je;
-        uint64_t eo = oe;
-        Row ew = we;
-        uint32_t te = toe;                 // SA[e]
-        if (view.ch(we) != c) {
-            ej = view.pred(je, c, cidx, ew);
-            if (ej == kNone) break;
-            eo = view.len(ej, ew) - 1;
-            te = toe_row[ej];
-        }
-        if (sj > ej || (sj == ej && so > eo)) break;
-        uint32_t nj = view.lf_row(sw);
-        uint64_t nt = (uint64_t)view.lf_off(sw) + so;
-        Row nw = view.load(nj);
-        count_fast_forward(view, nj, nt, nw);
-        uint32_t mj;
-        uint64_t mt;
-        Row mw;
-        if (sj == ej) {
-            mj = nj;
-            mt = nt + (eo - so);
-            mw = nw;
-        } else {
-            mj = view.lf_row(ew);
-            mt = (uint64_t)view.lf_off(ew) + eo;
-            mw = view.load(mj);
-        }
-        count_fast_forward(view, mj, mt, mw);
-        if (nj > mj || (nj == mj && nt > mt)) break;
-        js = nj; os = nt; ws = nw;
-        je = mj; oe = mt; we = mw;
-        toe = te - 1;
-    }
-    uint64_t occ = 0;
-    if (k > 0) occ = view.idx(je) + oe - (view.idx(js) + os) + 1;
-    mlen_out[rd] = (uint32_t)k;
-    occ_out[rd] = occ;
-    const uint32_t want = (uint32_t)min(occ, (uint64_t)max_occ);
-    uint64_t *out = pos_out + rd * max_occ;
-    uint32_t x = toe;
-    for (uint32_t t = 0; t < want; ++t) {
-        out[t] = x;
-        if (t + 1 < want) x = phi_step(phi, x);
-    }
-    for (uint32_t t = want; t < max_occ; ++t) out[t] = kLocateNone;
+    longest_suffix<true, true>(view, toe_row, bases, read_off, n_reads, order,
+                               [&](uint64_t rd, uint64_t k, const SearchRange<V> &R) {
+                                   uint64_t occ = 0;
+                                   if (k > 0) occ = view.idx(R.je) + R.oe - (view.idx(R.js) + R.os) + 1;
+                                   mlen_out[rd] = (uint32_t)k;
+                                   occ_out[rd] = occ;
+                                   const uint32_t want = (uint32_t)min(occ, (uint64_t)max_occ);
+                                   uint64_t *out = pos_out + rd * max_occ;
+                                   uint32_t x = R.toe;
+                                   for (uint32_t t = 0; t < want; ++t) {
+                                       out[t] = x;
+                                       if (t + 1 < want) x = phi_step(phi, x);
+                                   }
+                                   for (uint32_t t = want; t < max_occ; ++t) out[t] = kLocateNone;
+                               });
 }
 
 // ---- attach: the per-row toehold table of the layout in HBM -------------------------------------
@@ -167,30 +103,14 @@ __global__ void phi_dir_kernel(const uint2 *pair, uint64_t s, uint32_t shift, ui
 }
 
 // Row flags -> the rows that end a run, in order (d_sel, room for every row), their number in *d_count.
-template <class V>
-inline hipError_t run_end_rows_view(const V &view, uint32_t rows, uint8_t *d_flag, uint32_t *d_sel,
-                                    unsigned long long *d_count, void *d_tmp, size_t tmp_bytes, hipStream_t stream) {
-    hipLaunchKernelGGL(run_end_flags_kernel<V>, dim3(locate_grid(rows)), dim3(kLocBlock), 0, stream, view, d_flag);
-    return hipcub::DeviceSelect::Flagged(d_tmp, tmp_bytes, hipcub::CountingInputIterator<uint32_t>(0), d_flag, d_sel, d_count,
-                                         (size_t)rows, stream);
-}
-
 inline hipError_t run_end_rows(const Index &ix, uint8_t *d_flag, uint32_t *d_sel, unsigned long long *d_count, void *d_tmp,
                                size_t tmp_bytes, hipStream_t stream) {
     const uint32_t rows = (uint32_t)ix.table_rows();
-    if (ix.line_rows()) return run_end_rows_view(CountFatView{ix.table_fat()}, rows, d_flag, d_sel, d_count, d_tmp, tmp_bytes, stream);
-    if (ix.layout() == 3) return run_end_rows_view(CountSKView<3>{ix.table_k()}, rows, d_flag, d_sel, d_count, d_tmp, tmp_bytes, stream);
-    if (ix.layout() == 2) return run_end_rows_view(CountSKView<2>{ix.table_k()}, rows, d_flag, d_sel, d_count, d_tmp, tmp_bytes, stream);
-    return run_end_rows_view(CountOneStepView{ix.table()}, rows, d_flag, d_sel, d_count, d_tmp, tmp_bytes, stream);
-}
-
-template <typename View>
-inline void launch_locate_view(const View &view, const uint32_t *toe_row, const PhiTable &phi, const uint8_t *d_bases,
-                               const uint64_t *d_read_off, uint64_t n_reads, uint32_t max_occ, uint32_t *d_mlen, uint64_t *d_occ,
-                               uint64_t *d_pos, const uint32_t *d_order, hipStream_t stream) {
-    const dim3 grid((uint32_t)((n_reads + kQueryBlock - 1) / kQueryBlock)), block(kQueryBlock);
-    hipLaunchKernelGGL(locate_kernel<View>, grid, block, 0, stream, view, toe_row, phi, d_bases, d_read_off, n_reads, max_occ,
-                       d_mlen, d_occ, d_pos, d_order);
+    return with_view(ix, [&](auto view) {
+        hipLaunchKernelGGL(run_end_flags_kernel<decltype(view)>, dim3(locate_grid(rows)), dim3(kLocBlock), 0, stream, view, d_flag);
+        return hipcub::DeviceSelect::Flagged(d_tmp, tmp_bytes, hipcub::CountingInputIterator<uint32_t>(0), d_flag, d_sel, d_count,
+                                             (size_t)rows, stream);
+    });
 }
 
 // Locate queries over whatever layout the index holds; toe_row / phi were built for that layout.
@@ -198,18 +118,10 @@ inline void launch_locate(const Index &ix, const uint32_t *toe_row, const PhiTab
                           const uint64_t *d_read_off, uint64_t n_reads, uint32_t max_occ, uint32_t *d_mlen, uint64_t *d_occ,
                           uint64_t *d_pos, const uint32_t *d_order, hipStream_t stream) {
     if (n_reads == 0) return;
-    if (ix.line_rows())
-        launch_locate_view(CountFatView{ix.table_fat()}, toe_row, phi, d_bases, d_read_off, n_reads, max_occ, d_mlen, d_occ, d_pos,
-                           d_order, stream);
-    else if (ix.layout() == 3)
-        launch_locate_view(CountSKView<3>{ix.table_k()}, toe_row, phi, d_bases, d_read_off, n_reads, max_occ, d_mlen, d_occ, d_pos,
-                           d_order, stream);
-    else if (ix.layout() == 2)
-        launch_locate_view(CountSKView<2>{ix.table_k()}, toe_row, phi, d_bases, d_read_off, n_reads, max_occ, d_mlen, d_occ, d_pos,
-                           d_order, stream);
-    else
-        launch_locate_view(CountOneStepView{ix.table()}, toe_row, phi, d_bases, d_read_off, n_reads, max_occ, d_mlen, d_occ, d_pos,
-                           d_order, stream);
+    with_view(ix, [&](auto view) {
+        hipLaunchKernelGGL(locate_kernel<decltype(view)>, read_grid(n_reads), dim3(kQueryBlock), 0, stream, view, toe_row, phi,
+                           d_bases, d_read_off, n_reads, max_occ, d_mlen, d_occ, d_pos, d_order);
+    });
 }
 
 }  // namespace colbwt
