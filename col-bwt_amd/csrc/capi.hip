@@ -1414,7 +1414,7 @@ int colbwt_index_info(const colbwt_index *idx, colbwt_info *out) {
     out->layout_shape = idx->ix.line_rows() ? (idx->ix.table_fat().steps << 8) | kFatSlotSteps : 0;
     out->table_rows = idx->ix.table_rows();
     out->n_devices = 1 + (uint32_t)idx->more.size();
-    out->reserved_ = 0;
+    out->tail_permille = idx->ix.line_rows() ? idx->ix.table_fat().tail_permille : 0;
     return COLBWT_OK;
 }
 

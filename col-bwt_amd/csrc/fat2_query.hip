@@ -36,7 +36,8 @@ constexpr uint32_t kOffMis0 = 0xFFFFFFFCu;      // the lane's line is a mismatch
 constexpr uint32_t kOffMis1 = 0xFFFFFFFBu;      // ... second half.  In this state L holds the col id to report for the mismatching base.
 
 #ifdef COLBWT_COUNT_TRIPS
-#define FAT2_STAT(k) (++stat[k])
+#define FAT2_STAT(k) (++stat[k])   // row trips, fast-forward, entry trips, scan, absent, idle, row to entry, match-tail trips
+__device__ unsigned long long g_fat2_more[2];   // K = 8: row trips whose 8 bases all matched (the match-tail trips among them); match-tail trips that consumed 15 (arrival with the row's own base consumed)
 #else
 #define FAT2_STAT(k) ((void)0)
 #endif
@@ -57,16 +58,23 @@ void fat2_query_kernel(FatTable T, const uint8_t *__restrict__ bases, const uint
                        uint64_t n_reads, uint32_t big_reads, uint32_t tail_permille,
                        PmlT *__restrict__ pml, uint8_t *__restrict__ cid) {
     constexpr bool kWide = sizeof(PmlT) == 4;
+    constexpr bool kTail = K == 8 && !kWide;       // these rows carry a match tail (fat_layout.h) and this kernel walks it
     __shared__ uint4 s_stage[kWaves][8][64];       // per wave: instruction q's 64 x 16 bytes
     __shared__ uint4 s_win[kWaves][4][64];         // read bytes (lane_io.h LaneWindow)
     __shared__ uint32_t s_claim;                   // the workgroup's chunk counter (ChunkPlan)
     __shared__ uint8_t s_top[256];                 // byte -> index among the four most frequent characters (mis_slot)
+    __shared__ uint32_t s_tch[kTail ? 256 : 1];    // match tail: a byte of TCH (four 2-bit indices) -> the four characters
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u, g8 = lane & ~7u, p = lane & 7u;
     uint32_t *const s_jx = reinterpret_cast<uint32_t *>(&s_stage[wave][7][48]);   // 64 dwords
     ChunkPlan plan;
     plan.init(n_reads, big_reads, tail_permille);
     if (threadIdx.x == 0) s_claim = 0;
     s_top[threadIdx.x] = (uint8_t)fat_top_index(T.top4, threadIdx.x);
+    if constexpr (kTail) {
+        const uint32_t b = threadIdx.x;
+        s_tch[b] = ((T.top4 >> (8 * (b & 3u))) & 0xFFu) | (((T.top4 >> (8 * ((b >> 2) & 3u))) & 0xFFu) << 8) |
+                   (((T.top4 >> (8 * ((b >> 4) & 3u))) & 0xFFu) << 16) | (((T.top4 >> (8 * (b >> 6))) & 0xFFu) << 24);
+    }
     __syncthreads();
     uint32_t *const claim = &s_claim;
     ReadCursor rc;
@@ -91,7 +99,7 @@ void fat2_query_kernel(FatTable T, const uint8_t *__restrict__ bases, const uint
     const uint4 *const my_row = &s_stage[wave][p][g8];
 
 #ifdef COLBWT_COUNT_TRIPS
-    unsigned long long stat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long stat[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stat_full = 0, stat_hop15 = 0;
 #endif
     while (__any(!done)) {
         // ---- (1) where the lane stands (registers and LDS only, fat_query.hip).  A lane whose chunk is
@@ -130,7 +138,11 @@ void fat2_query_kernel(FatTable T, const uint8_t *__restrict__ bases, const uint
                                                  16, 0, 0);
         }
         // ---- (3) the trip's other memory traffic, behind the lines
-        if (live && win.avail(g) < (k < 8u ? (uint32_t)k : 8u)) win.request(my_win, bases, g);
+        // a lane that has matched 8 bases or more may want the 16 of a match-tail trip; one that is lost
+        // (short lengths; on an entry L is a col id) refills as late as ever
+        uint32_t want = 8u;
+        if constexpr (kTail) want = T.match_tail && L >= 8u && o != kOffMis0 && o != kOffMis1 ? 16u : 8u;
+        if (live && win.avail(g) < (k < want ? (uint32_t)k : want)) win.request(my_win, bases, g);
         if (step_back) { rc.in_next = read_off[rc.r - 1]; rc.next_in_flight = true; }
         if (!done && rc.fetch_pending) rc.request_chunk(plan, read_off);
         lds_dma_landed();
@@ -140,7 +152,7 @@ void fat2_query_kernel(FatTable T, const uint8_t *__restrict__ bases, const uint
         // what the trip reports: `consumed` bases, lengths l_new - e for element e (keep = 0: all 0),
         // col ids byte e of `ids`; pushed once below, whatever kind of line the lane had
         uint32_t consumed = 0, l_new = 0, keep = 0xFFFFFFFFu, keep1 = 0xFFFFFFFFu;
-        uint64_t ids = 0;
+        uint64_t ids = 0, ids2 = 0;                          // ids2: elements 8 .. 15 of a match-tail trip
         if (!live || have == 0) FAT2_STAT(5);
         if (live && have != 0) {
             const uint64_t W = win.get8(my_win, lane, g);    // byte 7 = the next base
@@ -248,6 +260,24 @@ void fat2_query_kernel(FatTable T, const uint8_t *__restrict__ bases, const uint
                     uint32_t steps = run < cap ? run : cap;
                     bool own_jump = true, to_entry = false;
                     uint32_t e_next = 0, carry = 0;
+                    // ---- the match tail: all 8 matched, the row knows the next 8 steps of this position
+                    // (o < TSPAN), the read and the window hold 8 more bases, and the collector has room
+                    // for 16 now and 8 in every trip left before the flush (lane_out.h).  All or nothing:
+                    // a base of the second 8 that differs leaves the trip what it was.
+                    bool hop = false;
+                    uint4 tl = make_uint4(0u, 0u, 0u, 0u);
+                    if constexpr (kTail) {
+                        if (T.match_tail && run == 8u && left + skip >= 16u && o < (r1.x >> 24) &&
+                            acc.cnt + 16u + 8u * (3u - (trip & 3u)) <= 96u) {
+                            tl = my_row[7 ^ p];              // TCID | TI | TO, TCH
+                            const uint64_t W2 = win.get8(my_win, lane, g - (8u - skip));
+                            const uint64_t TC = (uint64_t)s_tch[(tl.w >> 16) & 0xFFu] | ((uint64_t)s_tch[tl.w >> 24] << 32);
+                            hop = W2 == TC;
+                        }
+                    }
+#ifdef COLBWT_COUNT_TRIPS
+                    if (K == 8 && run == 8u && cap == 8u) ++stat_full;       // row trips whose 8 bases all match
+#endif
                     if (run < cap) {
                         // a base that is there differs from the character met after `run` steps
                         // (:516 / :520): depth d = run + 1 <= K, the base after the consumed ones
@@ -284,13 +314,24 @@ void fat2_query_kernel(FatTable T, const uint8_t *__restrict__ bases, const uint
                             l_new = steps - 1;
                         }
                     } else {
-                        consumed = steps - skip;
+                        consumed = (hop ? 16u : steps) - skip;
                         l_new = L + consumed;                // :517 ++length per matching base
                     }
                     L = l_new;
                     ids = steps ? CID >> (8u * (8u - steps)) : 0ull;     // element e <-> step steps - e
+                    if (hop) {
+                        FAT2_STAT(7);
+#ifdef COLBWT_COUNT_TRIPS
+                        stat_hop15 += skip;
+#endif
+                        ids2 = ids;                          // elements 8 .. 15: the row's own steps; 0 .. 7: the tail's
+                        ids = (uint64_t)tl.x | ((uint64_t)tl.y << 32);
+                    }
                     if (k == consumed) {
                         // the read is done: its last LF (:527) has no observable effect
+                    } else if (hop) {
+                        j = tl.z;                            // exact for every o < TSPAN: no cut, no fast-forward
+                        o += tl.w & 0xFFFFu;
                     } else if (to_entry) {
                         FAT2_STAT(6);
                         j = T.slot_line0 + (kDeep ? e_next : e_next >> 1);
@@ -324,7 +365,8 @@ void fat2_query_kernel(FatTable T, const uint8_t *__restrict__ bases, const uint
                     cid[g - consumed + 1 + e] = (uint8_t)(ids >> (8 * e));
                 }
             } else {
-                acc.push_run(consumed, l_new, keep, keep1, (uint32_t)ids, (uint32_t)(ids >> 32));
+                if constexpr (kTail) acc.template push_run<true>(consumed, l_new, keep, keep1, (uint32_t)ids, (uint32_t)(ids >> 32), (uint32_t)ids2, (uint32_t)(ids2 >> 32));
+                else acc.push_run(consumed, l_new, keep, keep1, (uint32_t)ids, (uint32_t)(ids >> 32));
             }
             k -= consumed;
         }
@@ -345,6 +387,8 @@ void fat2_query_kernel(FatTable T, const uint8_t *__restrict__ bases, const uint
     }
 #ifdef COLBWT_COUNT_TRIPS
     for (int q = 0; q < 8; ++q) atomicAdd(&g_fat_stats[q], stat[q]);
+    atomicAdd(&g_fat2_more[0], stat_full);
+    atomicAdd(&g_fat2_more[1], stat_hop15);
 #endif
 }
 
@@ -370,11 +414,14 @@ void launch_fat2_query(const FatTable &T, const uint8_t *d_bases, const uint64_t
 }
 
 #ifdef COLBWT_COUNT_TRIPS
-extern "C" int colbwt_debug_fat2_stats(unsigned long long *out8, int reset) {
-    if (hipMemcpyFromSymbol(out8, HIP_SYMBOL(g_fat_stats), 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
+// out10: the eight counters of FAT2_STAT, then the two of g_fat2_more
+extern "C" int colbwt_debug_fat2_stats(unsigned long long *out10, int reset) {
+    if (hipMemcpyFromSymbol(out10, HIP_SYMBOL(g_fat_stats), 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
+    if (hipMemcpyFromSymbol(out10 + 8, HIP_SYMBOL(g_fat2_more), 2 * sizeof(unsigned long long)) != hipSuccess) return -1;
     if (reset) {
         unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_fat_stats), z, sizeof(z)) != hipSuccess) return -1;
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_fat2_more), z, 2 * sizeof(unsigned long long)) != hipSuccess) return -1;
     }
     return 0;
 }

@@ -223,10 +223,11 @@ __global__ __launch_bounds__(256) void fat_slot_flags_kernel(PlainLevel P, FatTa
 }
 
 // kMis = false: rows with in-row mismatch slots; true: rows of the mismatch-line variant (rho,
-// sflags: the arrays of the two kernels above).
+// sflags: the arrays of the two kernels above; tail_rows: counts the rows that get a match tail).
 template <int K, bool kMis>
 __global__ __launch_bounds__(256) void fat_pack_kernel(PlainLevel P, FatTable T, const uint32_t *__restrict__ rho,
-                                                       const uint8_t *__restrict__ sflags, uint8_t *__restrict__ lines) {
+                                                       const uint8_t *__restrict__ sflags, uint8_t *__restrict__ lines,
+                                                       unsigned long long *__restrict__ tail_rows) {
     const uint64_t i64 = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (i64 >= P.r) return;
     const uint32_t i = (uint32_t)i64;
@@ -278,6 +279,40 @@ __global__ __launch_bounds__(256) void fat_pack_kernel(PlainLevel P, FatTable T,
         put_byte(w, kFatCut + (s - 1), cut | (len_b << 4));
     }
 
+    if constexpr (kMis && K == 8) {
+        // ---- the match tail (fat_layout.h): steps 9 .. 16 of the row's leading `span` positions.
+        // (j, t) = LF^8(first position).  Positions first .. first + span - 1 of one row have
+        // consecutive images; as long as the image of that prefix lies inside ONE level-K row before
+        // a step, the step meets that row's character and col id for all of them and keeps the
+        // images consecutive.  The same after step 16 makes (TI, TO + o) the exact landing of
+        // position o: it is where the query's own two 8-step jumps -- (I[8], O[8] + o) here, then
+        // the jump of that row, cuts and fast-forward included -- put it, since both are the row
+        // and offset of the same text position and a position inside its row has one such form.
+        uint64_t span = len < kFatTSpanMax ? len : kFatTSpanMax;
+        uint32_t tch = 0;
+        for (uint32_t a = 1; a <= kFatTailSteps + 1; ++a) {              // before steps 9 .. 16, and after step 16
+            const uint64_t jl = P.idx[(uint64_t)j + 1] - P.idx[j];
+            const uint64_t room = t < jl ? jl - t : 0;                   // positions of row j from the image on
+            span = span < room ? span : room;
+            if (a > kFatTailSteps) break;
+            const uint32_t meta = P.meta[j];
+            const uint32_t x = fat_top_index(T.top4, meta & 0xFFu);
+            if (x >= 4) span = 0;                                        // two bits cannot say it
+            tch |= (x & 3u) << (2 * (8 - a));
+            put_byte(w, kFatTCid + (8 - a), meta >> 8);
+            plain_lf(P, j, t);
+        }
+        if (span != 0) {
+            put_half(w, kFatTCh, tch);
+            w[kFatTI / 4] = j;
+            put_half(w, kFatTO, (uint32_t)t);
+            put_byte(w, kFatTSpan, (uint32_t)span);
+            atomicAdd(tail_rows, 1ull);
+        } else {
+            w[kFatTCid / 4] = 0;                                         // a row without a tail keeps its spare bytes zero
+            w[kFatTCid / 4 + 1] = 0;
+        }
+    }
     if constexpr (kMis) {
         put_byte(w, kFatFlags, sflags[i]);
     } else {
@@ -505,7 +540,7 @@ int build_fat_steps(const DevTable &T1, const HintChars &chars, int mismatch_lin
 
     clock.lap("  characters, jump tables");
     // ---- origin rows and which of their mismatch entries exist (mismatch-line variant)
-    DevPtr rho_buf, rho_first_buf, sflags_buf;
+    DevPtr rho_buf, rho_first_buf, sflags_buf, tail_rows_buf;
     uint64_t mis_lines = 0;
     uint32_t *d_rho = nullptr, *d_rho_first = nullptr;     // raw pointers for the launches
     uint8_t *d_sflags = nullptr;
@@ -556,8 +591,11 @@ int build_fat_steps(const DevTable &T1, const HintChars &chars, int mismatch_lin
     uint8_t *const d_lines = buf.lines.as<uint8_t>();
     SK_TRY(hipMemset(d_lines + (uint64_t)r * kFatRowBytes, 0, kFatRowBytes));
     if (mismatch_lines) {
+        SK_TRY(tail_rows_buf.alloc(sizeof(unsigned long long)));
+        unsigned long long *const d_tail_rows = tail_rows_buf.as<unsigned long long>();
+        SK_TRY(hipMemset(d_tail_rows, 0, sizeof(unsigned long long)));
         hipLaunchKernelGGL((fat_pack_kernel<K, true>), dim3(nblocks), dim3(256), 0, 0, cur, out, (const uint32_t *)d_rho,
-                           (const uint8_t *)d_sflags, d_lines);
+                           (const uint8_t *)d_sflags, d_lines, d_tail_rows);
         SK_TRY(hipGetLastError());
         uint8_t *const d_entries = d_lines + ((uint64_t)r + 1) * kFatRowBytes;
         if (mis_lines) SK_TRY(hipMemset(d_entries + (mis_lines - 1) * kFatRowBytes, 0, kFatRowBytes));   // the odd half of the last line
@@ -570,12 +608,22 @@ int build_fat_steps(const DevTable &T1, const HintChars &chars, int mismatch_lin
                                (const uint32_t *)d_rho, (const uint32_t *)d_rho_first, (const uint8_t *)d_sflags, d_entries);
     } else {
         hipLaunchKernelGGL((fat_pack_kernel<K, false>), dim3(nblocks), dim3(256), 0, 0, cur, out, (const uint32_t *)nullptr,
-                           (const uint8_t *)nullptr, d_lines);
+                           (const uint8_t *)nullptr, d_lines, (unsigned long long *)nullptr);
     }
     SK_TRY(hipGetLastError());
     SK_TRY(hipStreamSynchronize(0));
     out.lines = d_lines;
-    clock.lap("  lines packed");
+    if (mismatch_lines && K == 8) {
+        // the match tail (fat_layout.h): how many rows carry one, and whether the query may use it
+        unsigned long long tail_rows = 0;
+        SK_TRY(hipMemcpy(&tail_rows, tail_rows_buf.as<unsigned long long>(), sizeof(tail_rows), hipMemcpyDeviceToHost));
+        out.tail_permille = (uint32_t)((tail_rows * 1000 + r - 1) / r);
+        const char *e = getenv("COLBWT_MATCH_TAIL");                 // "0": A/B runs and tests switch the hop off on one build
+        out.match_tail = e && atoi(e) == 0 ? 0u : 1u;
+    }
+    // with mismatch lines at K = 8 the pack pass also chases the 8 steps of the match tail: 16 + 1
+    // dependent LF steps per row instead of 8 + 1
+    clock.lap(mismatch_lines && K == 8 ? "  lines packed (with match tails)" : "  lines packed");
     buf.idx = std::move(cur_buf.idx);
     buf.thr = std::move(cur_buf.thr);
     cur_buf.release();          // I, O, meta: only the pack pass read them

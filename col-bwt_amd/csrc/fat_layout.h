@@ -60,6 +60,19 @@
 //     its origin row and which of ITS entries exist.  If the base after those two mismatches as
 //     well, the lane goes from entry to entry: a stretch of mismatches costs a line fill per two
 //     bases, and a trip never ends on a row just to learn that it mismatches.
+//   * MATCH TAIL (K = 8 only): a row whose 8 characters all match costs a line fill per 8 bases
+//     just to walk on.  Row bytes [112, 128) and byte 19 hold the NEXT 8 steps for the leading
+//     TSPAN positions of the row -- those whose images stay inside ONE row after each of 8 .. 16
+//     LF steps, so that what they meet and where they land is again a constant of the row:
+//       [112, 120)  TCID   tcid[a] at byte 8 - a: the col id reported after 7 + a LF steps (CID's order)
+//       [120, 124)  TI     row holding LF^16(first position of the row)
+//       [124, 126)  TO     offset of that image inside TI: position o < TSPAN lands at (TI, TO + o)
+//                          exactly -- no cut, no fast-forward -- where two 8-step jumps of the
+//                          query take it
+//       [126, 128)  TCH    tch[a] at bits 2 (8 - a): index among the four most frequent characters
+//                          of the character met after 7 + a LF steps (TCH's bytes decode to CH's order)
+//       [19]        TSPAN  0 = no tail (a tail character outside the top four, or K != 8); <= 255
+//     A lane at offset o < TSPAN whose 16 next bases match CH and TCH consumes all 16 in one trip.
 // Entry dwords: [0] J1 | [1] P1 | t1 << 16 | d1 << 24 | [2..5] J[0..3] | [6..9] rho[0..3] |
 //   [10..11] P[0..3] halfwords | [12] ch[0..3] bytes | [13] cid[0..3] bytes |
 //   [14] v1 | vo[0] << 4 | vo[1] << 8 | vo[2] << 12 | vo[3] << 16 (3 valid bits each) | [15] 0.
@@ -93,6 +106,9 @@ constexpr uint32_t kFatSlotP = 8, kFatSlotCh2 = 12, kFatSlotCid2 = 13;
 // rows of the mismatch-line variant: valid bits of the origin row met after a - 1 steps at bits
 // 3 (a - 1) of the three bytes at kFatVal; RHO[a] dwords at kFatRho
 constexpr uint32_t kFatVal = 28, kFatRho = 80;
+// ... and their match tail (K = 8): the steps 9 .. 16 of the row's leading kFatTSpan positions
+constexpr uint32_t kFatTSpan = 19, kFatTCid = 112, kFatTI = 120, kFatTO = 124, kFatTCh = 126;
+constexpr uint32_t kFatTailSteps = 8, kFatTSpanMax = 255;
 // a mismatch entry
 constexpr uint32_t kMisBytes = 64, kMisJ1 = 0, kMisP1 = 1, kMisJ = 2, kMisRho = 6, kMisP = 10, kMisCh = 12, kMisCid = 13, kMisVal = 14;
 constexpr uint32_t kMisDeep = 16;        // dword offset of the second half of a deep entry: the same fields one step further
@@ -114,6 +130,8 @@ struct FatTable {
     uint32_t slot_line0;      // mismatch-line variant: line number (128-byte units of `lines`) of entry 0; 0 = in-row slots
     uint32_t n_rho;           // origin rows (entries: 3 per origin row)
     uint32_t entry_shift;     // log2 of the bytes per mismatch entry: 6, or 7 = deep entries
+    uint32_t match_tail;      // 1: the query may use the rows' match tails (K = 8 mismatch-line rows; COLBWT_MATCH_TAIL=0 at open: 0)
+    uint32_t tail_permille;   // rows with TSPAN > 0, per mille of all rows (rounded up)
 };
 
 // byte / halfword / dword k of a row image held as dwords

@@ -24,7 +24,13 @@
 //     stores it, a col-id piece is re-aligned from the dumped bytes -- one store instruction per 64
 //     pieces, and the partial pieces at the ragged ends go out byte by byte, 64 bytes per
 //     instruction.  About six store instructions per flush, 1.5 per trip.
-// Capacity: a lane keeps fewer than 64 elements after a flush and adds at most 8 per trip: 96.
+// Capacity: 96 elements, and the invariant is cnt <= 96 whenever a push has been made.  A lane keeps
+// fewer than 64 elements after a flush.  A plain trip adds at most 8: 63 + 4 x 8 = 95.  A trip of
+// the match tail (fat2_query.hip) adds up to 16 in ONE push, and only when the lane's count says
+// there is room for it and for 8 more in each trip left until the flush: in the trip of phase
+// ph = trip & 3 it needs cnt + 16 + 8 (3 - ph) <= 96, else the lane takes the plain 8.  By
+// induction cnt <= 72 + 8 ph after the trip of phase ph, 96 at the flush; and since a period adds
+// at most 64 to fewer than 64, what a flush finds above a block boundary is never more than a block.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -53,10 +59,12 @@ struct OutRuns {
     uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0, c4 = 0, c5 = 0, c6 = 0, c7 = 0, c8 = 0, c9 = 0, c10 = 0, c11 = 0, c12 = 0, c13 = 0, c14 = 0, c15 = 0, c16 = 0, c17 = 0, c18 = 0, c19 = 0, c20 = 0, c21 = 0, c22 = 0, c23 = 0;
     uint32_t cnt = 0;
 
-    // n <= 8 elements: PML values l_new - e for element e (keep / keep1 = 0: elements 0-1 / 2-3 are 0
-    // instead: what a mismatch entry reports), col ids = byte e of ids_lo | ids_hi << 32
+    // n <= 8 elements (kUpTo16: n <= 16): PML values l_new - e for element e (keep / keep1 = 0:
+    // elements 0-1 / 2-3 are 0 instead: what a mismatch entry reports), col ids = byte e of
+    // ids_lo | ids_hi << 32 (elements 8 .. 15: of ids2_lo | ids2_hi << 32)
+    template <bool kUpTo16 = false>
     __device__ __forceinline__ void push_run(uint32_t n, uint32_t l_new, uint32_t keep, uint32_t keep1, uint32_t ids_lo,
-                                             uint32_t ids_hi) {
+                                             uint32_t ids_hi, uint32_t ids2_lo = 0, uint32_t ids2_hi = 0) {
         const uint32_t in_run = (1u << n) - 1u;
         uint32_t p0 = l_new < n ? 1u << l_new : 0u;                  // the element whose value is 0
         p0 |= (keep ? 0u : 3u) & in_run;
@@ -70,6 +78,33 @@ struct OutRuns {
         z1b = (uint32_t)(((((uint64_t)z1b << 32) | z1a) << n) >> 32);
         z1a = (z1a << n) | p1;
         // ---- col ids: up by n bytes = (n >> 2) dwords, then (n & 3) bytes
+        if constexpr (kUpTo16) {
+            const bool d8 = n & 16u;
+            c23 = d8 ? c19 : c23;
+            c22 = d8 ? c18 : c22;
+            c21 = d8 ? c17 : c21;
+            c20 = d8 ? c16 : c20;
+            c19 = d8 ? c15 : c19;
+            c18 = d8 ? c14 : c18;
+            c17 = d8 ? c13 : c17;
+            c16 = d8 ? c12 : c16;
+            c15 = d8 ? c11 : c15;
+            c14 = d8 ? c10 : c14;
+            c13 = d8 ? c9 : c13;
+            c12 = d8 ? c8 : c12;
+            c11 = d8 ? c7 : c11;
+            c10 = d8 ? c6 : c10;
+            c9 = d8 ? c5 : c9;
+            c8 = d8 ? c4 : c8;
+            c7 = d8 ? c3 : c7;
+            c6 = d8 ? c2 : c6;
+            c5 = d8 ? c1 : c5;
+            c4 = d8 ? c0 : c4;
+            c3 = d8 ? 0u : c3;
+            c2 = d8 ? 0u : c2;
+            c1 = d8 ? 0u : c1;
+            c0 = d8 ? 0u : c0;
+        }
         const bool d4 = n & 8u, d2 = n & 4u;
         c23 = d4 ? c21 : c23;
         c22 = d4 ? c20 : c22;
@@ -148,6 +183,12 @@ struct OutRuns {
         const uint32_t mhi = n >= 8 ? 0xFFFFFFFFu : (n > 4 ? (1u << (8 * (n - 4))) - 1u : 0u);
         c0 |= ids_lo & mlo;
         c1 |= ids_hi & mhi;
+        if constexpr (kUpTo16) {
+            const uint32_t m2 = n >= 12 ? 0xFFFFFFFFu : (n > 8 ? (1u << (8 * (n - 8))) - 1u : 0u);
+            const uint32_t m3 = n >= 16 ? 0xFFFFFFFFu : (n > 12 ? (1u << (8 * (n - 12))) - 1u : 0u);
+            c2 |= ids2_lo & m2;
+            c3 |= ids2_hi & m3;
+        }
         cnt += n;
     }
 

@@ -63,7 +63,7 @@ typedef struct colbwt_info {
     uint32_t layout_shape; /* line rows: own steps << 8 | steps per mismatch slot; else 0 */
     uint64_t table_rows;   /* rows of the HBM table actually queried   */
     uint32_t n_devices;    /* replicas of the table (colbwt_index_open_devices); the fields above describe the first */
-    uint32_t reserved_;
+    uint32_t tail_permille; /* K = 8 rows of a mismatch-line layout that carry a match tail, per mille (rounded up); else 0 */
 } colbwt_info;
 
 typedef struct colbwt_stats {

@@ -44,7 +44,11 @@ def main():
     torch.cuda.synchronize()
     stats_fn(out, 1)
     if a.layout in (5, 6):
-        names = ["row_trips", "fast_forward", "entry_trips", "scan", "absent", "idle", "row_to_entry", "unused"]
+        # tail_trips: row trips that consumed 16 bases through the row's match tail (K = 8; COLBWT_MATCH_TAIL=0
+        # switches them off); full_match_trips: row trips whose 8 bases all matched, those included;
+        # tail_trips_15: tail trips that arrived with the row's own base already consumed
+        names = ["row_trips", "fast_forward", "entry_trips", "scan", "absent", "idle", "row_to_entry", "tail_trips",
+                 "full_match_trips", "tail_trips_15"]
     else:
         names = ["live", "fast_forward", "slot", "scan", "absent", "idle", "chunk_ends", "skip_arrivals"]
     d = {k: int(v) for k, v in zip(names, out)}
@@ -53,7 +57,8 @@ def main():
               "flush": out[14] / wave_trips, "other_requests": out[9] / wave_trips, "wait": out[10] / wave_trips,
               "compute": out[11] / wave_trips} if a.layout not in (5, 6) else {}
     d.update(kernel_ms=st.kernel_ms, per_read={k: round(v / n, 3) for k, v in d.items()}, rows=int(tbl.info().table_rows),
-             steps=a.steps, layout=a.layout, clocks=clocks, resets=float((d_pml[:n * m] == 0).float().mean().item()))
+             steps=a.steps, layout=a.layout, clocks=clocks, tail_permille=int(tbl.info().tail_permille),
+             match_tail=os.environ.get("COLBWT_MATCH_TAIL", "1"), resets=float((d_pml[:n * m] == 0).float().mean().item()))
     print(json.dumps(d))
 
 
